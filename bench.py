@@ -5,9 +5,22 @@ Metric (BASELINE.json): Mpixels/s of the fused adaptive-warp (FilterInterpolatio
 fp32, batch 32 of 1280x720 frames per GPU, synthetic inputs already resident in HBM.  One "step" = one pass of
 the operator over one batch (one kernel launch through the C ABI, on torch's current stream).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing else: set up, pre-warm and warm up, time ONE window of exactly K
+steps, write the last step's output if `--dump-outputs` asks for it, print the line.  `--full` adds everything else the
+line can carry, as before: the median of 7 windows, the GPU span of a window and every launch's own duration (`roofline`,
+`config.window_gpu_us_per_step`), the `dist` record at N > 1, and at N = 1 the CPU baseline with its `check` of the
+output against the oracle, the i.i.d.-flow, padded-layout and calibration rows, and the other BASELINE configs as
+`secondary` rows.
+
+--dump-outputs DIR: what the timed path's last step computed, i.e. the output tensor a caller of
+FilterInterpolationLayer_gpu_forward receives, as float32 .npy files (prefixed `rank<r>_` at N > 1): the whole output
+when it is at most 48 MB, otherwise `output_frame0.npy` (the first frame pair's output) and `output_sample.npy`, the
+values at a fixed, seeded set of flat indices (`output_sample_index.npy`, float64, exact).  The inputs are seeded, so two
+builds run with the same arguments can be compared file for file.
 
 Multi-GPU: frame pairs are independent, so the batch is sharded over the ranks and there is no collective on the
 data path; RCCL is used only to broadcast the run configuration from rank 0 before the timed region and to take the
@@ -15,8 +28,9 @@ max of the per-rank times after it.  Default = STRONG scaling, as BASELINE.json 
 the global batch stays 32 frame pairs and rank r owns the contiguous shard of 32 / N of them (32 / 16 / 8 / 4 per GPU
 at N = 1 / 2 / 4 / 8); `--scaling weak` gives every rank its own batch of 32 instead (global batch 32 N).
 
-Timing: W warm-up steps, then R (`--windows`, 7) windows of exactly K steps.  A window is  barrier + synchronize | t0 | K
-launches | the rank's own synchronize | t1  -- no collective and no event inside the clock; `value` comes from the MEDIAN
+Timing: W warm-up steps, then R (`--windows`: 1, or 7 with `--full`) windows of exactly K steps.  A window is
+barrier + synchronize | t0 | K launches | the rank's own synchronize | t1  -- no collective and no event inside the
+clock; `value` comes from the MEDIAN
 window, each window's time being the max over the ranks (one all-reduce after the last window).  A shard of 4 frames is a
 66 us launch and the host enqueues one in ~10 us: eager launches keep the queue full (`--launch graph` replays the K steps
 from one captured HIP graph instead; it starts a 20-step window ~35 us later and is no faster at 300 steps).
@@ -218,6 +232,33 @@ def check_against_oracle(out, want):
     err = float(np.abs(got.astype(np.float64) - want.astype(np.float64)).max())
     return {"max_abs_err": err, "frames": int(nb), "tolerance": CHECK_TOLERANCE, "ok": bool(err <= CHECK_TOLERANCE),
             "against": "oracle (CPU restatement of my_lib.c), same input tensors as the timed launches"}
+
+
+DUMP_WHOLE_MAX_BYTES = 48 << 20     # up to this the whole output is written; beyond it, the first frame and a fixed sample
+DUMP_FRAME0_MAX_BYTES = 24 << 20    # ... the first frame pair's output, when it is no larger than this
+DUMP_SAMPLE = 1 << 21               # flat indices drawn for the sample (fewer after removing repeats)
+DUMP_SAMPLE_SEED = 20251015
+
+
+def dump_outputs(out, directory, prefix=""):
+    """`--dump-outputs`: the output tensor of the last timed step as float32 .npy files under `directory` (module
+    docstring); at most 48 MB.  The sample's indices depend on the output's size and DUMP_SAMPLE_SEED only."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    torch.cuda.synchronize(out.device)
+    files = {}
+    if out.numel() * 4 <= DUMP_WHOLE_MAX_BYTES:
+        files["output"] = out.detach().float().cpu().numpy()
+    else:
+        flat = out.detach().reshape(-1)
+        idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, flat.numel(), DUMP_SAMPLE, dtype=np.int64))
+        if out[0].numel() * 4 <= DUMP_FRAME0_MAX_BYTES:
+            files["output_frame0"] = out[0].detach().float().cpu().numpy()
+        files["output_sample"] = flat.index_select(0, torch.from_numpy(idx).to(out.device)).float().cpu().numpy()
+        files["output_sample_index"] = idx.astype(np.float64)           # exact below 2^53
+    for name, arr in files.items():
+        np.save(os.path.join(directory, prefix + name + ".npy"), arr)
 
 
 def kernel_source_hash():
@@ -519,8 +560,14 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=100)
-    ap.add_argument("--windows", type=int, default=7,
-                    help="repetitions of the K-step timed window; `value` is the MEDIAN window (max over ranks per window)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: 7 windows, per-launch and roofline figures, the dist record, and "
+                         "at N = 1 the CPU baseline, the oracle check and the secondary rows (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR/*.npy (float32, at most 64 MB)")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="repetitions of the K-step timed window (default 1; 7 with --full); `value` is the MEDIAN window "
+                         "(max over ranks per window)")
     ap.add_argument("--prewarm", type=int, default=200,
                     help="untimed launches before the warm-up steps: the device needs ~100 launches (60 ms) to "
                          "reach its steady clocks (tools/timeline.py); never part of the timed region")
@@ -529,7 +576,8 @@ def main(argv=None):
     ap.add_argument("--launch", default="eager", choices=["auto", "eager", "graph"],
                     help="graph: the K steps of a window are one captured HIP graph replay (auto = eager: see main)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the rows outside the timed region (i.i.d. flow, the other BASELINE configs, copy calibration)")
+                    help="with --full: skip the rows outside the timed region (i.i.d. flow, the other BASELINE configs, copy "
+                         "calibration)")
     ap.add_argument("--input-sets", type=int, default=0,
                     help="input sets the launches rotate over (0 = automatic: enough to cycle >= 2.8 GB, what the full batch "
                          "moves per launch -- a smaller shard re-launched on the same tensors is partly served by the 256 MB "
@@ -538,7 +586,7 @@ def main(argv=None):
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--channels", type=int, default=3)
     ap.add_argument("--flow", default="smooth", choices=["smooth", "iid"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the oracle check")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU work the cpu_baseline leg is bounded to")
     # plumbing test of the N > 1 path on a box with fewer GPUs than ranks (ranks share devices, gloo instead of
     # RCCL, which refuses two ranks on one device): the line it prints is NOT a measurement
@@ -546,6 +594,8 @@ def main(argv=None):
     # one rank, but through torch.distributed on backend nccl (= RCCL): see _FORCE_DIST above
     ap.add_argument("--dist-single", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
+    if args.windows is None:
+        args.windows = 7 if args.full else 1
 
     import torch
     rank, local_rank, world = dist_env()
@@ -600,11 +650,13 @@ def main(argv=None):
     x, flow, filt, out = sets[0]
     steps, warmup, windows = cfg["steps"], cfg["warmup"], cfg["windows"]
     counter = [0]
+    last_out = [None]                           # the output tensor the latest step() launch writes
 
     def step(ev=None):
         # one pass of the hot path over the batch; events (instrumented pass only) sit on the stream the kernel is launched on
         xi, fi, ki, oi = sets[counter[0] % nsets]
         counter[0] += 1
+        last_out[0] = oi
         if ev is not None:
             ev[0].record()
         err = my_lib.FilterInterpolationLayer_gpu_forward(xi, fi, ki, oi)
@@ -629,6 +681,7 @@ def main(argv=None):
         with torch.cuda.graph(graph, stream=side):
             for _ in range(steps):
                 step()
+        graph_last_out = last_out[0]            # what the last node of every replay writes
         for _ in range(warmup):
             step()
         with torch.cuda.stream(side):
@@ -652,8 +705,38 @@ def main(argv=None):
             return launch_stream
     worst_w, local_w = timed_windows(window, windows, world, device)
     worst, local = median(worst_w), median(local_w)
-    # Outside the clock: (i) the same K steps bracketed by ONE HIP event pair on the launch stream -- the GPU-side span of a
-    # window; (ii) eager: the same K launches with an event pair around EACH -- the dominant kernel's own duration
+    if args.dump_outputs:
+        # before anything else is launched: the buffer the last timed step wrote
+        dump_outputs(graph_last_out if use_graph else last_out[0], args.dump_outputs,
+                     "rank%d_" % rank if world > 1 else "")
+    value = plan["global_batch"] * H * W * steps / worst / 1e6          # all ranks' sites per step
+    workload = "FilterInterpolation fwd fs=4 C=%d batch=%d %dx%d fp32 flow=%s" % (C, cfg["batch"], W, H, args.flow)
+    line = {
+        "metric": "Mpixels/s adaptive-warp fwd @720p batch32",
+        "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+        "ms_per_step": round(worst / steps * 1e3, 4), "higher_is_better": True, "scaling": args.scaling,
+        "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic" if not args.share_gpu else "synthetic; PLUMBING TEST (ranks share a GPU), not a measurement",
+        "config": {"workload": workload, "batch_per_gpu": B, "global_batch": plan["global_batch"],
+                   "prewarm_launches": args.prewarm, "launch": "hip_graph" if use_graph else "eager",
+                   "windows": windows, "window": "median of %d windows of %d steps; clock: barrier + synchronize | t0 | "
+                                                 "%d steps | this rank's synchronize | t1; max over ranks per window" % (
+                                                     windows, steps, steps),
+                   "window_ms_min_max": [round(min(worst_w) * 1e3, 4), round(max(worst_w) * 1e3, 4)],
+                   "window_host_enqueue_us": round(median(timed_windows.last_enqueue_s) * 1e6, 1),
+                   "input_sets": nsets,
+                   "sharding": "independent frame pairs, contiguous shards per rank, no data-path collective"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if _dist_on(world):
+            import torch.distributed as dist
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    # --full.  Outside the clock: (i) the same K steps bracketed by ONE HIP event pair on the launch stream -- the GPU-side
+    # span of a window; (ii) eager: the same K launches with an event pair around EACH -- the dominant kernel's own duration
     spans = []
     for r in range(3):
         barrier_sync(world, device)
@@ -679,8 +762,6 @@ def main(argv=None):
         avg_kernel_s = sum(per_launch_us) / steps / 1e6
     barrier_us = barrier_cost_us(world, device)
     achieved = alg_bytes / avg_kernel_s                                 # B/s, this rank's dominant kernel
-    total_sites = plan["global_batch"] * H * W                          # all ranks' sites per step
-    value = total_sites * steps / worst / 1e6
     dist_seen = None
     if _dist_on(world):
         # what the collective layer actually saw (evidence fields; nothing here is on the data path)
@@ -761,32 +842,15 @@ def main(argv=None):
                 secondary["rows"]["config4_memc_net_star_4x1280x720"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
 
     if rank == 0:
-        workload = "FilterInterpolation fwd fs=4 C=%d batch=%d %dx%d fp32 flow=%s" % (C, cfg["batch"], W, H, args.flow)
         traffic, traffic_source = load_traffic(workload) if B == cfg["batch"] else (None, None)   # (full batch only)
-        line = {
-            "metric": "Mpixels/s adaptive-warp fwd @720p batch32",
-            "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-            "ms_per_step": round(worst / steps * 1e3, 4), "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic" if not args.share_gpu else "synthetic; PLUMBING TEST (ranks share a GPU), not a measurement",
-            "config": {"workload": workload, "batch_per_gpu": B, "global_batch": plan["global_batch"],
-                       "prewarm_launches": args.prewarm, "launch": "hip_graph" if use_graph else "eager",
-                       "windows": windows, "window": "median of %d windows of %d steps; clock: barrier + synchronize | t0 | "
-                                                     "%d steps | this rank's synchronize | t1; max over ranks per window" % (
-                                                         windows, steps, steps),
-                       "window_ms_min_max": [round(min(worst_w) * 1e3, 4), round(max(worst_w) * 1e3, 4)],
-                       "window_gpu_us_per_step": round(window_gpu_s / steps * 1e6, 2),
-                       "window_host_enqueue_us": round(median(timed_windows.last_enqueue_s) * 1e6, 1),
-                       "window_fixed_cost_us": round((worst - window_gpu_s) * 1e6, 1),   # wall - GPU span of the median window
-                       "input_sets": nsets,
-                       "sharding": "independent frame pairs, contiguous shards per rank, no data-path collective"},
-            "roofline": {"bound": "hbm", "achieved": round(achieved / 1e9, 1), "peak": HBM_PEAK_BPS / 1e9,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_BPS, 4),
-                         "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": "fi_fwd", "algorithmic_bytes_per_launch": alg_bytes,
-                         "avg_launch_us": round(avg_kernel_s * 1e6, 2),
-                         "first_launches_us": [round(v, 2) for v in per_launch_us[:4]] if per_launch_us else None},
-        }
+        line["config"]["window_gpu_us_per_step"] = round(window_gpu_s / steps * 1e6, 2)
+        line["config"]["window_fixed_cost_us"] = round((worst - window_gpu_s) * 1e6, 1)   # wall - GPU span of the median window
+        line["roofline"] = {"bound": "hbm", "achieved": round(achieved / 1e9, 1), "peak": HBM_PEAK_BPS / 1e9,
+                            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_BPS, 4),
+                            "traffic": traffic, "traffic_source": traffic_source,
+                            "kernel": "fi_fwd", "algorithmic_bytes_per_launch": alg_bytes,
+                            "avg_launch_us": round(avg_kernel_s * 1e6, 2),
+                            "first_launches_us": [round(v, 2) for v in per_launch_us[:4]] if per_launch_us else None}
         if secondary:
             # achievable_peak: what this box's HBM gives the tiled kernels' access pattern in this run (the better of a copy
             # and the kernel's own 7 : 1 read : write mix, memc_calibration_stream); the spec peak stays `peak`

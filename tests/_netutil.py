@@ -53,6 +53,40 @@ def grad_l1_by_module(net):
     return acc
 
 
+GRAD_SAMPLE = 1024
+
+
+def grad_sample_positions(name, numel, argmax):
+    """Flat positions of a parameter's gradient that tests/golden/reference_star_64.npz records: GRAD_SAMPLE drawn with a
+    seed derived from the parameter's NAME, plus `argmax` (the position of the largest |g|); sorted, unique."""
+    import numpy as np
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    idx = rng.integers(0, numel, min(numel, GRAD_SAMPLE), dtype=np.int64)
+    return np.unique(np.append(idx, int(argmax)))
+
+
+def quantize(values, step):
+    """Integers q with |values - q * step| <= step / 2 (the recorded form of a fixture array; see dequantize)."""
+    import numpy as np
+    return np.rint(np.asarray(values, dtype=np.float64) / step).astype(np.int32)
+
+
+def dequantize(q, step):
+    import numpy as np
+    return q.astype(np.float64) * step
+
+
+def to_byte_planes(q):
+    """int32 array -> (4, n) uint8, byte k of every element in row k (compresses far better than the interleaved bytes)."""
+    import numpy as np
+    return np.ascontiguousarray(np.asarray(q, dtype="<i4").reshape(-1).view(np.uint8).reshape(-1, 4).T)
+
+
+def from_byte_planes(planes):
+    import numpy as np
+    return np.ascontiguousarray(planes.T).view("<i4").reshape(-1)
+
+
 def import_reference_networks():
     """Imports the reference's `networks` package (needs /root/reference on disk) with stand-ins for the
     modules it imports at module scope but never uses on the inference path."""

@@ -1,11 +1,13 @@
-"""The drop-in claim, at the import surface: the reference's own, UNMODIFIED `networks/MEMC_Net_star.py` is imported
-from /root/reference with the REAL `memc-net_amd/my_package` (the ctypes loader over libmemc_hip.so -- not the
-oracle-backed stand-in the other network tests install) on `sys.path`.  It must construct, its operator modules must
-be this repository's classes, and the first operator call on CPU tensors must fail with the loader's "no CPU path"
-error -- i.e. the reference code reached the real HIP binding and nothing fell back.
+"""The drop-in claim, at the import surface: what the reference's own, UNMODIFIED `networks` modules import from
+`my_package` (recorded in tests/golden/reference_imports.json by make_golden_reference_class.py while the reference
+package was imported) resolves, with the REAL `memc-net_amd/my_package` (the ctypes loader over libmemc_hip.so -- not
+the oracle-backed stand-in the other network tests install) on `sys.path`, to this repository's classes; the network
+built on them constructs, and the first operator call on CPU tensors fails with the loader's "no CPU path" error --
+i.e. the reference's import lines reach the real HIP binding and nothing falls back.
 
-CPU only; skipped where /root/reference does not exist (the GPU box).  On a GPU the same reference file running on
-the HIP operators is covered by tests/test_gpu_network.py."""
+CPU only.  On a GPU the same network running on the HIP operators is covered by tests/test_gpu_network.py."""
+import importlib
+import json
 import os
 import sys
 
@@ -15,9 +17,6 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import _netutil      # noqa: E402
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(_netutil.REF_ROOT, "networks")),
-                                reason="needs the reference tree at /root/reference")
 
 
 def _fresh_real_my_package():
@@ -30,18 +29,30 @@ def _fresh_real_my_package():
 
 def test_unmodified_reference_network_reaches_the_real_loader():
     my_lib = _fresh_real_my_package()
-    ref = _netutil.import_reference_networks()
+    with open(os.path.join(HERE, "golden", "reference_imports.json")) as f:
+        imports = json.load(f)["imports"]
+    importers = {e["importer"] for e in imports}
+    assert {"networks.MEMC_Net", "networks.MEMC_Net_star"} <= importers
     try:
-        assert ref.__file__.startswith(_netutil.REF_ROOT)
-        star = sys.modules["networks.MEMC_Net_star"]
-        # the names the reference imports (MEMC_Net_star.py:6-7) resolved to this repository's classes
+        # every name the reference's network modules import (MEMC_Net_star.py:6-7 and the others) resolves to a class
+        # of this repository's my_package
+        for e in imports:
+            mod = importlib.import_module(e["module"])
+            assert "memc-net_amd" in mod.__file__, e
+            for name in e["names"]:
+                cls = getattr(mod, name)
+                assert isinstance(cls, type) and issubclass(cls, torch.nn.Module), e
+        assert sys.modules["my_package._ext.my_lib"] is my_lib
         from my_package.modules.FilterInterpolationModule import FilterInterpolationModule
         from my_package.modules.FlowProjectionModule import FlowProjectionModule
-        assert star.FilterInterpolationModule is FilterInterpolationModule
-        assert star.FlowProjectionModule is FlowProjectionModule
-        assert sys.modules["my_package._ext.my_lib"] is my_lib
-        net = ref.MEMC_Net_star(channel=3, filter_size=4, training=False).eval()
+        _netutil.purge_networks()
+        import networks
+        assert "memc-net_amd" in networks.__file__
+        net = networks.MEMC_Net_star(channel=3, filter_size=4, training=False).eval()
         assert sum(p.numel() for p in net.parameters()) == 70312501
+        base = sys.modules["networks._base"]         # where the network binds the operator classes it calls
+        assert base.FilterInterpolationModule is FilterInterpolationModule
+        assert base.FlowProjectionModule is FlowProjectionModule
         x = _netutil.frames(3, 1, 128, 128)
         with torch.no_grad(), pytest.raises(RuntimeError, match="no CPU path"):
             net(x)                                   # first custom operator on the path: FlowProjectionModule

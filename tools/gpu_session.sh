@@ -16,21 +16,21 @@ echo "== pytest";  timeout 1800 python -m pytest tests -m gpu -q 2>&1 | tail -15
 cp gpurun_out/parity_errors.json "$OUT/parity_errors.json" 2>/dev/null
 echo "== sweep (product library)";   timeout 900 python tools/bench_ops.py ${QUICK:+--quick} --json "$OUT/bench_ops.json" 2>&1 | grep -v amdgpu.ids | tee "$OUT/bench_ops.log"
 echo "== baselines (reference kernels on this GPU, CPU oracle)"; timeout 900 python tests/bench_baselines.py --json "$OUT/baselines.json" 2>&1 | grep -v amdgpu.ids | tee "$OUT/baselines.log"
-echo "== bench";   timeout 900 python bench.py 2>&1 | tail -3 | tee "$OUT/bench.log"
+echo "== bench";   timeout 900 python bench.py --full 2>&1 | tail -3 | tee "$OUT/bench.log"
 echo "== bench at the driver's arguments (--steps 20 --warmup 5), whole line"
-timeout 900 python bench.py --steps 20 --warmup 5 2>&1 | tail -1 | tee "$OUT/bench_driver_args.log" | cut -c1-400
+timeout 900 python bench.py --full --steps 20 --warmup 5 2>&1 | tail -1 | tee "$OUT/bench_driver_args.log" | cut -c1-400
 echo "== bench, strong-scaling shard sizes on one GPU (what rank 0 of an N-GPU run executes: batch 32 / N, rotating input sets), at the driver's 20 steps and at 300"
-for b in 32 16 8 4; do for st in 20 300; do timeout 300 python bench.py --batch $b --steps $st --warmup 5 --no-cpu-baseline --no-secondary 2>&1 | tail -1 | tee -a "$OUT/bench_shards.log" | python -c "
+for b in 32 16 8 4; do for st in 20 300; do timeout 300 python bench.py --full --batch $b --steps $st --warmup 5 --no-cpu-baseline --no-secondary 2>&1 | tail -1 | tee -a "$OUT/bench_shards.log" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['config']; r=d['roofline']
 print('batch %2d steps %3d %-9s value %9.1f ms/step %.4f gpu_us/step %.2f enqueue_us %.1f fixed_us %.1f kernel_us %.2f first %s windows %s' % (c['batch_per_gpu'], d['steps'], c['launch'], d['value'], d['ms_per_step'], c['window_gpu_us_per_step'], c['window_host_enqueue_us'], c['window_fixed_cost_us'], r['avg_launch_us'], r['first_launches_us'], c['window_ms_min_max']))" | tee -a "$OUT/bench_shards_summary.txt"; done; done
 echo "== the N > 1 code path on this one GPU: two ranks sharing it over gloo (PLUMBING, not a measurement), 20 and 300 steps"
 echo "== the collective layer on a one-rank RCCL communicator (backend nccl on this one GPU)"
-timeout 600 python bench.py --dist-single --steps 20 --warmup 5 --no-cpu-baseline --no-secondary 2>&1 | grep '^{"metric"' | tee "$OUT/bench_dist_single.log" | python -c "
+timeout 600 python bench.py --full --dist-single --steps 20 --warmup 5 --no-cpu-baseline --no-secondary 2>&1 | grep '^{"metric"' | tee "$OUT/bench_dist_single.log" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('one-rank RCCL communicator:', json.dumps(d['dist']))" | tee -a "$OUT/bench_shards_summary.txt"
 T0=$(date +%s.%N)
-for st in 20 300; do timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29641 bench.py --gpus 2 --share-gpu --batch 8 --steps $st --warmup 5 2>&1 | grep '^{"metric"' | tee -a "$OUT/bench_share_gpu.log" | python -c "
+for st in 20 300; do timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29641 bench.py --full --gpus 2 --share-gpu --batch 8 --steps $st --warmup 5 2>&1 | grep '^{"metric"' | tee -a "$OUT/bench_share_gpu.log" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('2 ranks on one GPU: steps %3d ms/step %.4f barrier_us %s per-rank ms/step %s' % (d['steps'], d['ms_per_step'], d['dist']['barrier_us'], d['dist']['per_rank_ms_per_step']))" | tee -a "$OUT/bench_shards_summary.txt"; done
@@ -55,7 +55,7 @@ echo "== SQ counters of the owner kernel"
 bash tools/pmc_sq.sh $TAG/sq proj "proj_owner5<false" 2>&1 | tail -45 | tee "$OUT/proj_owner5_sq.txt"
 cd /tmp && export TMPDIR=/tmp
 echo "== rocprof kernel trace of bench.py (the same command as the bench line above, minus the CPU baseline and the secondary rows)"
-timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_trace" -o bench -- python "$REPO/bench.py" --no-cpu-baseline --no-secondary > "$OUT/prof_trace.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_trace" -o bench -- python "$REPO/bench.py" --full --no-cpu-baseline --no-secondary > "$OUT/prof_trace.log" 2>&1
 grep '^{"metric"' "$OUT/prof_trace.log" | tail -1 > "$OUT/bench_line_profiled_run.json"    # the bench line of THIS process
 python "$REPO/tools/prof_summary.py" stats "$OUT/prof_trace/bench_results.db" --tail 300 --out "$OUT/bench_kernel_stats.txt" | grep -v "^at::\|^$" | head -6
 rm -rf "$OUT/prof_trace"

@@ -52,7 +52,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "pmc"))
     ap.add_argument("--kernel", default="fi_fwd_tiled")
-    ap.add_argument("--bench-args", default="--steps 6 --warmup 2 --no-cpu-baseline --no-secondary --launch eager")
+    ap.add_argument("--bench-args", default="--full --steps 6 --warmup 2 --no-cpu-baseline --no-secondary --launch eager")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     py = sys.executable
