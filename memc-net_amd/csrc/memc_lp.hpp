@@ -1,0 +1,134 @@
+// memc_lp.hpp -- half-width storage for the adaptive-warp forward of libmemc_hip_lp.so (lp_filter_interpolation.hip).
+//
+// Numerics contract (include/memc_warp_lp.h):
+//   * payload type T in {fp16, bf16}: the image / features, the filter taps, the occlusions (blend) and the output;
+//   * the flow is fp32 or T, decoded in the kernel;
+//   * every input is widened to fp32 exactly; the tap products, the quadrant sums and the bilinear blend are the fp32
+//     kernels' (filter_interpolation.hip) in the same order;
+//   * the output is rounded to T ONCE, round-to-nearest-even, overflow to +-inf -- exactly what `tensor.to(T)` does;
+//   * sites outside the image copy the input pixel (widened and narrowed again: exact).
+//
+// The LDS image is the fp32 kernels' (memc_tile.hpp): one f32x4 pixel quad per pixel.  Only the global side narrows: a
+// quad of four T is 8 bytes, so the tiled kernels need quads that are 8-byte aligned -- widths a multiple of four, row /
+// channel / batch strides multiples of four elements, 8-byte aligned bases (the launcher checks; everything else takes
+// the one-lane-per-site kernel).
+#pragma once
+
+#include "memc_tile.hpp"
+
+namespace memc {
+
+// storage tags: the element type in memory and its exact widening / single rounding
+struct F32 {
+    using st = float;
+};
+struct F16 {
+    using st = unsigned short;
+};
+struct BF16 {
+    using st = unsigned short;
+};
+template <class S>
+using st_t = typename S::st;
+
+typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+typedef u16x4 u16x4a __attribute__((aligned(8)));         // a quad of four halves in global memory: 8-byte aligned
+
+template <class S> __device__ __forceinline__ float widen(st_t<S> v);
+template <> __device__ __forceinline__ float widen<F32>(float v) { return v; }
+template <> __device__ __forceinline__ float widen<F16>(unsigned short v) { return (float)__builtin_bit_cast(_Float16, v); }
+template <> __device__ __forceinline__ float widen<BF16>(unsigned short v)
+{
+    return __builtin_bit_cast(float, (unsigned)v << 16);
+}
+
+// fp32 -> T, round-to-nearest-even, overflow to +-inf (v_cvt_f16_f32 / v_cvt_pk_bf16_f32)
+template <class S> __device__ __forceinline__ st_t<S> narrow(float v);
+template <> __device__ __forceinline__ float narrow<F32>(float v) { return v; }
+template <> __device__ __forceinline__ unsigned short narrow<F16>(float v)
+{
+    return __builtin_bit_cast(unsigned short, (_Float16)v);
+}
+template <> __device__ __forceinline__ unsigned short narrow<BF16>(float v)
+{
+    return __builtin_bit_cast(unsigned short, (__bf16)v);
+}
+
+template <class S>
+__device__ __forceinline__ f32x4 widen4(const u16x4 &q)
+{
+    return f32x4{widen<S>(q[0]), widen<S>(q[1]), widen<S>(q[2]), widen<S>(q[3])};
+}
+
+// quad loads, widened: streamed (non-temporal; flow, taps, occlusions) and cached (the image)
+template <class S>
+__device__ __forceinline__ f32x4 ld4_stream(const st_t<S> *p)
+{
+    if constexpr (sizeof(st_t<S>) == 4) return ld_stream4(reinterpret_cast<const float *>(p));
+    else return widen4<S>(__builtin_nontemporal_load(reinterpret_cast<const u16x4a *>(p)));
+}
+template <class S>
+__device__ __forceinline__ f32x4 ld4_cached(const st_t<S> *p)
+{
+    if constexpr (sizeof(st_t<S>) == 4) return ld_cached4(reinterpret_cast<const float *>(p));
+    else return widen4<S>(*reinterpret_cast<const u16x4a *>(p));
+}
+// narrowed quad store (non-temporal: the output is single-use)
+template <class S>
+__device__ __forceinline__ void st4_stream(st_t<S> *p, const f32x4 &v)
+{
+    const u16x4 q = {narrow<S>(v[0]), narrow<S>(v[1]), narrow<S>(v[2]), narrow<S>(v[3])};
+    __builtin_nontemporal_store(q, reinterpret_cast<u16x4a *>(p));
+}
+
+// Staging of NCH (1..4) T planes into the fp32 pixel-quad LDS image of memc_tile.hpp: the same slots and the same
+// unconditional loads as tile_stage_load_planes (an empty slot reads the plane's first quad), 8 bytes per quad; widened
+// when written to LDS.
+template <int NCH>
+struct LpStageRegs {
+    uint2 v[kStageIts][NCH];               // a quad of four T as two packed dwords
+};
+
+// the two halves of a packed dword, widened
+template <class S> __device__ __forceinline__ float widen_lo(unsigned w) { return widen<S>((unsigned short)(w & 0xFFFFu)); }
+template <class S> __device__ __forceinline__ float widen_hi(unsigned w) { return widen<S>((unsigned short)(w >> 16)); }
+template <> __device__ __forceinline__ float widen_lo<BF16>(unsigned w) { return __builtin_bit_cast(float, w << 16); }
+template <> __device__ __forceinline__ float widen_hi<BF16>(unsigned w) { return __builtin_bit_cast(float, w & 0xFFFF0000u); }
+
+template <int NCH>
+__device__ __forceinline__ void lp_stage_load(const Region &r, const StageSlot &sl,
+                                              const unsigned short *const (&plane)[NCH], int hstride, LpStageRegs<NCH> &sr)
+{
+#pragma unroll
+    for (int it = 0; it < kStageIts; it++) {
+        const bool on = sl.row[it] < r.h;
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            const unsigned short *p = on ? plane[c] + (int64_t)(r.y0 + sl.row[it]) * hstride + r.x0 + 4 * sl.q[it] : plane[c];
+            sr.v[it][c] = *reinterpret_cast<const uint2 *>(p);
+        }
+    }
+}
+
+template <class T, int NCH>
+__device__ __forceinline__ void lp_stage_store(const Region &r, const StageSlot &sl, const LpStageRegs<NCH> &sr, f32x4 *tile)
+{
+#pragma unroll
+    for (int it = 0; it < kStageIts; it++) {
+        if (sl.row[it] < r.h) {
+            f32x4 *dst = tile + sl.row[it] * r.pitch;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                f32x4 px = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int c = 0; c < NCH; c++) {
+                    const unsigned wd = i < 2 ? sr.v[it][c].x : sr.v[it][c].y;
+                    px[c] = (i & 1) ? widen_hi<T>(wd) : widen_lo<T>(wd);
+                }
+                dst[swz_col(4 * sl.q[it] + i)] = px;
+            }
+        }
+    }
+}
+
+}  // namespace memc

@@ -11,7 +11,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 import my_package._ext.my_lib as my_lib
-from ._common import check, f32c, require_gpu
+from ._common import check, f32c, host_widened, require_gpu
 
 
 class _DepthFlowProjectionFunction(Function):
@@ -49,6 +49,6 @@ class DepthFlowProjectionLayer(object):
 
     def __call__(self, input1, input2):
         self.fillhole = 1 if self.requires_grad == False else 0    # noqa: E712
-        return _DepthFlowProjectionFunction.apply(input1, input2, self.fillhole)
+        return host_widened(_DepthFlowProjectionFunction.apply, input1, input1, input2, self.fillhole)   # fp16 / bf16: widened
 
     forward = __call__

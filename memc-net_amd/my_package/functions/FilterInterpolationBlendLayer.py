@@ -9,13 +9,20 @@ recomputations + two backward launches; nothing but the inputs is kept for it).
 
 The fused kernel covers what the networks use (RGB, 4x4 filters, widths a multiple of 4); any other shape is
 composed from FilterInterpolationLayer calls -- same values, no error.
+
+float16 / bfloat16 (functions/_common.py: payload_dtype): the payload dtype is torch.promote_types over the images, the
+taps and the occlusions, which are cast to it; the flows stay float32 or that dtype.  The forward is one kernel of
+libmemc_hip_lp.so for every shape (fp32 arithmetic, one rounding of the blended value).  The BACKWARD of a half call is
+not accelerated: the saved inputs are widened to float32, the float32 path above computes the gradients, and each comes
+back in its input's dtype.
 """
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 import my_package._ext.my_lib as my_lib
-from ._common import check, f32c, require_gpu
+import my_package._ext.my_lib_lp as my_lib_lp
+from ._common import cast, check, f32c, flow_dtype, payload_dtype, require_gpu
 from .FilterInterpolationLayer import FilterInterpolationLayer
 
 
@@ -72,10 +79,39 @@ class _FilterInterpolationBlendFunction(Function):
         return _blend_backward(ctx.saved_tensors, f32c(gradoutput))
 
 
+class _FilterInterpolationBlendLpFunction(Function):
+    """float16 / bfloat16: forward on libmemc_hip_lp.so; backward widened to float32 (not accelerated)"""
+
+    @staticmethod
+    def forward(ctx, input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):
+        args = tuple(t.contiguous() for t in (input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1))
+        output = torch.empty_like(args[0])                   # every element is written
+        check(my_lib_lp.FilterInterpolationBlendLayer_gpu_forward_lp(*args, output),
+              "FilterInterpolationBlendLayer_gpu_forward_lp")
+        ctx.save_for_backward(*args)
+        return output
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gradoutput):
+        saved = ctx.saved_tensors
+        grads = _blend_backward(tuple(t.float().contiguous() for t in saved), gradoutput.float().contiguous())
+        return tuple(g.to(t.dtype) for g, t in zip(grads, saved))
+
+
 class FilterInterpolationBlendLayer(object):
     """`FilterInterpolationBlendLayer()(input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1)`"""
 
     def __call__(self, input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):
+        require_gpu("FilterInterpolationBlendLayer", input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1)
+        dtype = payload_dtype(input0, input2, filter0, filter1, occlusion0, occlusion1)
+        if dtype != torch.float32:
+            fdt = flow_dtype(flow0, dtype) if flow_dtype(flow0, dtype) == flow_dtype(flow1, dtype) else torch.float32
+            return _FilterInterpolationBlendLpFunction.apply(
+                cast(input0, dtype), cast(input2, dtype), cast(flow0, fdt), cast(flow1, fdt), cast(filter0, dtype),
+                cast(filter1, dtype), cast(occlusion0, dtype), cast(occlusion1, dtype))
+        input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1 = (
+            cast(t, dtype) for t in (input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1))
         if fused_supported(input0, filter0, input2, flow0, flow1, filter1, occlusion0, occlusion1):
             return _FilterInterpolationBlendFunction.apply(input0, input2, flow0, flow1, filter0, filter1,
                                                            occlusion0, occlusion1)

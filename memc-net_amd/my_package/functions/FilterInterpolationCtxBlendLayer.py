@@ -61,6 +61,8 @@ class FilterInterpolationCtxBlendLayer(object):
     occlusion1)` -> (blended, warped ctx0, warped ctx2); the context outputs are detached."""
 
     def __call__(self, input0, input2, ctx0, ctx2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):
+        for t in (input0, input2, ctx0, ctx2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):
+            f32c(t)                                         # float32 only (its fallback warps would take half tensors)
         if fused_supported(input0, ctx0, filter0, occlusion0, input2, ctx2, flow0, flow1, filter1, occlusion1):
             return _CtxBlendFunction.apply(input0, input2, ctx0, ctx2, flow0, flow1, filter0, filter1, occlusion0,
                                            occlusion1)

@@ -4,6 +4,7 @@ The reference ships the C entry points (my_lib_cuda.h:53-68, my_lib.h:49-61) but
 follows the pattern of its InterpolationLayer.py.  On the GPU both share one kernel
 (my_lib_cuda.c:519,579).
 """
+from ._common import host_widened
 from .InterpolationLayer import _make_bilinear_function
 
 _InterpolationChFunction = _make_bilinear_function(
@@ -15,6 +16,6 @@ class InterpolationChLayer(object):
         super(InterpolationChLayer, self).__init__()
 
     def __call__(self, input1, input2):
-        return _InterpolationChFunction.apply(input1, input2)
+        return host_widened(_InterpolationChFunction.apply, input1, input1, input2)   # fp16 / bf16: widened on the host
 
     forward = __call__

@@ -9,7 +9,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 import my_package._ext.my_lib as my_lib
-from ._common import check, f32c, require_gpu
+from ._common import check, f32c, host_widened, require_gpu
 
 
 def _make_bilinear_function(label, fwd_name, bwd_name):
@@ -51,6 +51,6 @@ class InterpolationLayer(object):
         super(InterpolationLayer, self).__init__()
 
     def __call__(self, input1, input2):
-        return _InterpolationFunction.apply(input1, input2)
+        return host_widened(_InterpolationFunction.apply, input1, input1, input2)     # fp16 / bf16: widened on the host
 
     forward = __call__

@@ -25,3 +25,39 @@ def f32c(t):
     if t.dtype != torch.float32:
         raise TypeError("expected a float32 tensor, got %s" % t.dtype)
     return t.contiguous()
+
+
+# ---- the dtype rule of the operators (fp16 / bf16 next to float32) ----------------------------------------------------
+LOWP = (torch.float16, torch.bfloat16)
+
+
+def payload_dtype(*tensors):
+    """The payload dtype of a call: torch.promote_types over its payload tensors (image / features, filter taps,
+    occlusions).  float32 calls go exactly the old way; float16 / bfloat16 ones take libmemc_hip_lp.so where it has a
+    kernel.  Anything else raises TypeError."""
+    dt = tensors[0].dtype
+    for t in tensors[1:]:
+        dt = torch.promote_types(dt, t.dtype)
+    if dt != torch.float32 and dt not in LOWP:
+        raise TypeError("expected float32, float16 or bfloat16 tensors, got %s" % dt)
+    return dt
+
+
+def cast(t, dtype):
+    """`t` in `dtype` (through autograd: the gradient comes back in t's own dtype); no copy when it already is."""
+    return t if t.dtype == dtype else t.to(dtype)
+
+
+def flow_dtype(flow, payload):
+    """A flow is decoded in the half kernels when it is float32 or of the payload dtype; any other dtype is cast to
+    float32.  float32 payloads take float32 flows."""
+    return flow.dtype if payload in LOWP and flow.dtype in (torch.float32, payload) else torch.float32
+
+
+def host_widened(apply, like, *args):
+    """The operators without half kernels (FlowProjection, DepthFlowProjection, Interpolation, InterpolationCh):
+    float16 / bfloat16 tensors among `args` are widened to float32 on the host, `apply` (the float32 Function) runs, and
+    the result comes back in `like`'s dtype -- so that a cast model's concatenations and convolutions see one dtype.
+    Gradients flow back through the casts, each in its input's dtype.  Float32 arguments pass untouched."""
+    out = apply(*(cast(a, torch.float32) if isinstance(a, torch.Tensor) and a.dtype in LOWP else a for a in args))
+    return cast(out, like.dtype) if like.dtype in LOWP else out
