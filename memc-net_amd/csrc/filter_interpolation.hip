@@ -335,6 +335,13 @@ __global__ __launch_bounds__(NT, (NT == 256 && !RAGW) ? 2 : 1) void fi_fwd_tiled
 // three columns behind them go to fi_fwd_direct_fs4 (launcher).
 // CAP: the LDS budget in pixel quads (measurement arms only: 128 x 8 tiles need 4608 for their 137 x 21 boxes; RGB path only).
 // PHASE (measurement arm, RGB path): hold the results until the chip-wide write window of the 100 MHz clock opens (g_fi_phase).
+// xoff (run time, wave-uniform): the tile grid shifted xoff sites left, tile tx covering [kTW * tx - xoff, kTW * (tx + 1) - xoff)
+// (round 7; the launcher sizes the grid to ceil((W + xoff) / kTW) columns).  With rows of a multiple of 1 KiB an unshifted
+// 64-site tile row is one whole 256-B slot of a 4 KiB period and the 16 rows x 21 planes of a workgroup fall on 4 of its 16
+// slots; shifted by 32 sites every tile row is two 128-B lines in two adjacent slots, 8 per workgroup.
+// 0 or 32: a multiple of 4 keeps a lane's quad whole, and 16 / 48 would split 128-B lines (+37 % on the skeleton).  Lanes left
+// of the image are masked like those right of it and read clamped, in-range addresses.  (A run-time argument, not a template
+// parameter: the instantiations stay the ones the library has always shipped.)
 #ifdef MEMC_MEASURE
 __device__ unsigned g_fi_phase[2] = {1000u, 120u};         // period, window (ticks of 10 ns)
 #endif
@@ -343,7 +350,7 @@ __global__ __launch_bounds__(256, MINW) void fi_fwd_tiled_fs4(
     int W, int H, int C, int tiles_x, int tiles_y,
     int64_t s1b, int64_t s1c, int s1h, int64_t s2b, int64_t s2c, int s2h, int64_t s3b, int64_t s3c, int s3h,
     const float *__restrict__ in1, const float *__restrict__ flow, const float *__restrict__ filt,
-    float *__restrict__ out)
+    float *__restrict__ out, int xoff)
 {
     using G = TileGeom<LX, CAP>;
     constexpr int ITS = (CAP + 1023) / 1024;               // staging slots per lane (3 for the product's 3072)
@@ -368,16 +375,16 @@ __global__ __launch_bounds__(256, MINW) void fi_fwd_tiled_fs4(
         const TileCoord tc = strip_walk(blockIdx.x, gridDim.x, tiles_x, tiles_y, gridDim.x / (tiles_x * tiles_y));
         tx = tc.tx;  ty = tc.ty;  b = tc.b;
     }
-    const int tile_x0 = tx * G::kTW, tile_y0 = ty * G::kTH;
+    const int tile_x0 = tx * G::kTW - xoff, tile_y0 = ty * G::kTH;
     const int x = tile_x0 + 4 * (threadIdx.x % LX);
     const int y = tile_y0 + threadIdx.x / LX;
     const int Ws = RAGW ? W & ~3 : W;
-    const bool inb = x < Ws && y < H;         // Ws % 4 == 0: a lane's four sites are in or out together
+    const bool inb = x >= 0 && x < Ws && y < H;   // Ws % 4 == 0, xoff % 4 == 0: a lane's four sites are in or out together
 
     // 1. streams.  Loads are UNCONDITIONAL (lanes past the image edge read a clamped, in-range address and are
     // masked at the store): a load under `if` or `?:` makes its result a phi, and the compiler then waits
     // for it (s_waitcnt vmcnt(0)) at the join instead of at its first use, serialising every phase.
-    const int xs = min(x, Ws - 4), ys = min(y, H - 1);
+    const int xs = min(max(x, 0), Ws - 4), ys = min(y, H - 1);
     const float *flow_p = flow + b * s2b + (int64_t)ys * s2h + xs;
     const float *tap_p = filt + b * s3b + (int64_t)ys * s3h + xs;
     const f32x4 fx4 = ld_stream4(flow_p);
@@ -1145,15 +1152,16 @@ extern "C" int FilterInterpolationLayer_gpu_forward_kernel(
     if (w <= 0 || h <= 0 || channel <= 0 || batch <= 0) return 0;
     // production path: LDS-tiled, 16 B per lane (needs 4-element-aligned geometry)
     const bool vec = vec4_ok(w, {s1b, s1c, s1h, s2b, s2c, s2h, s3b, s3c, s3h}, {input1, input2, input3, output});
-#define MEMC_FI_TILED(LX, CT, MINW)   MEMC_FI_TILED_A(LX, CT, MINW, 0)
-#define MEMC_FI_TILED_A(LX, CT, MINW, WALK)                                                                     \
+#define MEMC_FI_TILED(LX, CT, MINW)   MEMC_FI_TILED_X(LX, CT, MINW, 0, 0)
+#define MEMC_FI_TILED_A(LX, CT, MINW, WALK) MEMC_FI_TILED_X(LX, CT, MINW, WALK, 0)
+#define MEMC_FI_TILED_X(LX, CT, MINW, WALK, XOFF)                                                               \
     do {                                                                                                   \
         using G = TileGeom<LX>;                                                                            \
-        const int ntx = (w + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;                        \
+        const int ntx = (w + (XOFF) + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;               \
         hipLaunchKernelGGL((fi_fwd_tiled_fs4<LX, CT, MINW, WALK>), dim3((unsigned)ntx * nty * batch), dim3(256), \
                            tile_lds_bytes<LX>(), stream, w, h, channel, ntx, nty, (int64_t)s1b,            \
                            (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, \
-                           s3h, input1, input2, input3, output);                                           \
+                           s3h, input1, input2, input3, output, XOFF);                                      \
     } while (0)
 #define MEMC_FI_C4N(SW) MEMC_FI_C4N_NT(SW, 256, false)
 #define MEMC_FI_C4N_NT(SW, NT, RAG) MEMC_FI_C4N_LX(SW, NT, RAG, 16)
@@ -1229,7 +1237,7 @@ extern "C" int FilterInterpolationLayer_gpu_forward_kernel(
 #define MEMC_FI_STRIPE(WALK, MINW)                                                                             \
             hipLaunchKernelGGL((fi_fwd_tiled_fs4<16, 3, MINW, WALK>), dim3(grid), dim3(256), tile_lds_bytes<16>(), \
                                stream, w, h, channel, ntx, nty, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b,     \
-                               (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output)
+                               (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output, 0)
             if (variant == 15) MEMC_FI_STRIPE(5, 2);
             else if (variant == 16) MEMC_FI_STRIPE(6, 2);
             else MEMC_FI_STRIPE(4, 2);                     // 17: row-major chunk per XCD at 2 waves/SIMD
@@ -1239,7 +1247,7 @@ extern "C" int FilterInterpolationLayer_gpu_forward_kernel(
             const int ntx = (w + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;
             hipLaunchKernelGGL((fi_fwd_tiled_fs4<16, 3, 2, 0, false, 3072, 1>), dim3((unsigned)ntx * nty * batch), dim3(256),
                                tile_lds_bytes<16>(), stream, w, h, channel, ntx, nty, (int64_t)s1b, (int64_t)s1c, s1h,
-                               (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output);
+                               (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output, 0);
         } else if (variant >= 20 && variant <= 25 && channel == 3) {
             // 20: 128 x 8 tiles (LX = 32) with a 4608-pixel budget, strips; 21: the same in hardware order; 22: 64 x 16 tiles
             // with a 4096-pixel budget (no band sweeps on i.i.d. flow); 23: 128 x 8 tiles on the product's 3072 pixels; 24 / 25:
@@ -1253,7 +1261,7 @@ extern "C" int FilterInterpolationLayer_gpu_forward_kernel(
                 hipLaunchKernelGGL((fi_fwd_tiled_fs4<LX, 3, MINW, WALK, false, CAP>), dim3((unsigned)ntx * nty * batch), \
                                    dim3(256), (tile_lds_bytes<LX, CAP>()), stream, w, h, channel, ntx, nty,       \
                                    (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h,              \
-                                   (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output);              \
+                                   (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output, 0);           \
             } while (0)
             if (variant == 20) MEMC_FI_WIDE(32, 0, 4608);
             else if (variant == 21) MEMC_FI_WIDE(32, 1, 4608);
@@ -1296,7 +1304,10 @@ extern "C" int FilterInterpolationLayer_gpu_forward_kernel(
             MEMC_FI_C4N(0);
         } else if (channel == 3) {                                     // default: 64x16 tiles, strip walk
             MEMC_PATH("fi_fwd:tiled_c3");
-            MEMC_FI_TILED(16, 3, 2);
+            // rows of a multiple of 1 KiB (720p, 4K): the tile grid shifted 32 sites left, 8 slots of 256 B per workgroup
+            // instead of 4 (fi_fwd_tiled_fs4: xoff).  From the strides the kernel is handed, not from the width: views are taken.
+            if (s1h % 256 == 0 && s3h % 256 == 0) MEMC_FI_TILED_X(16, 3, 2, 0, 32);
+            else MEMC_FI_TILED(16, 3, 2);
         } else if (channel >= 4) {                                     // any other count from four up: the same pipeline,
             MEMC_PATH("fi_fwd:tiled_c4n_ragged");                      // ragged last chunk
             MEMC_FI_C4N_NT(0, 256, true);
@@ -1326,7 +1337,7 @@ extern "C" int FilterInterpolationLayer_gpu_forward_kernel(
 #define MEMC_FI_TILED_RAGW(CT)                                                                                  \
         hipLaunchKernelGGL((fi_fwd_tiled_fs4<16, CT, 2, 0, true>), dim3((unsigned)ntx * nty * batch), dim3(256),    \
                            tile_lds_bytes<16>(), stream, w, h, channel, ntx, nty, (int64_t)s1b, (int64_t)s1c, s1h,   \
-                           (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output)
+                           (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output, 0)
 #define MEMC_FI_TAIL(CT)                                                                                        \
         hipLaunchKernelGGL((fi_fwd_direct_fs4<CT, 4>), dim3((unsigned)tail_y * batch), dim3(256), 0, stream, w, h,  \
                            channel, 1, tail_y, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h,     \
@@ -1361,6 +1372,7 @@ extern "C" int FilterInterpolationLayer_gpu_forward_kernel(
 #undef MEMC_FI_C4N_LX
 #undef MEMC_FI_TILED
 #undef MEMC_FI_TILED_A
+#undef MEMC_FI_TILED_X
     return launch_status();
 }
 

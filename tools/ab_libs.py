@@ -3,6 +3,7 @@
 than most single changes are worth: two builds can only be compared inside one process on one GPU).
 
     python tools/ab_libs.py <libA.so> <libB.so> [--op proj|proj_fill|depth_fill|fi_fwd|fi_bwd|fi_bwd_c64|interp_bwd_c64|ctx_img_blend|...] [--rounds 6] [--pan 40] [--scale 2]
+                            [--flow smooth|iid] [--shape BxHxW]
 
 Both libraries are loaded side by side (RTLD_LOCAL) and bound with my_package's own binder; launches alternate
 A, B, A, B ... in rounds, the median of each is printed."""
@@ -40,13 +41,15 @@ def main():
     ap.add_argument("--iters", type=int, default=12)
     ap.add_argument("--pan", type=float, default=0.0, help="camera pan (p, -p/2) px added to the benchmark's flow")
     ap.add_argument("--scale", type=float, default=1.0, help="the benchmark's flow times this")
+    ap.add_argument("--flow", default="smooth", choices=("smooth", "iid"), help="the flow the inputs are generated with")
+    ap.add_argument("--shape", default="32x720x1280", help="BxHxW of the main inputs (config 5: 8x2160x3840)")
     ap.add_argument("--prezero", action="store_true", help="zero-fill the projection's outputs in front of every timed call, outside "
                     "the timed span (what a caller that follows the reference's contract does: FlowProjectionLayer.py:27-28)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     libs = [Bound(os.path.abspath(p)) for p in a.libs]
-    B, H, W = 32, 720, 1280
-    t = synth.torch_inputs(dev, B, 3, H, W, flow_kind="smooth", with_depth=True, with_grad=True)
+    B, H, W = (int(v) for v in a.shape.split("x"))
+    t = synth.torch_inputs(dev, B, 3, H, W, flow_kind=a.flow, with_depth=True, with_grad=True)
     x, f, k, g, d = t["x"], t["flow"], t["filt"], t["gout"], t["depth"]
     if a.scale != 1.0 or a.pan != 0.0:
         f = (f * a.scale).contiguous()
@@ -56,7 +59,7 @@ def main():
     o3 = torch.zeros_like(x)
     g1, g2, g3 = torch.zeros_like(x), torch.zeros_like(f), torch.zeros_like(k)
     g2src, gd = torch.rand_like(f), torch.zeros_like(d)
-    c2 = synth.torch_inputs(dev, 8, 3, 256, 448, flow_kind="smooth")
+    c2 = synth.torch_inputs(dev, 8, 3, 256, 448, flow_kind=a.flow)
     c2o = torch.zeros_like(c2["x"])
     ops = {
         "proj": lambda l: l.FlowProjectionLayer_gpu_forward(f, cnt, out, 0),
@@ -86,10 +89,12 @@ def main():
     for op in a.op.split(","):
         fn = ops[op]
         ts = [[], []]
+        per_round = [[], []]                               # each round's median per library
         for r in range(a.rounds):
             for i, l in enumerate(libs):
                 for _ in range(4):
                     fn(l)
+                rt = []
                 for _ in range(a.iters):
                     if op in ("fi_bwd", "interp_bwd"):
                         g1.zero_()
@@ -97,10 +102,13 @@ def main():
                         cnt.zero_(); out.zero_()
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record(); fn(l); e1.record(); e1.synchronize()
-                    ts[i].append(e0.elapsed_time(e1) * 1e3)
+                    rt.append(e0.elapsed_time(e1) * 1e3)
+                ts[i] += rt
+                per_round[i].append(statistics.median(rt))
         ma, mb = statistics.median(ts[0]), statistics.median(ts[1])
-        print("%-12s A %8.1f us   B %8.1f us   B/A %.3f   (A = %s, B = %s)" % (
-            op, ma, mb, mb / ma, os.path.basename(a.libs[0]), os.path.basename(a.libs[1])), flush=True)
+        print("%-12s %s flow=%-6s A %8.1f us   B %8.1f us   B/A %.3f   rounds A %.1f..%.1f  B %.1f..%.1f   (A = %s, B = %s)" % (
+            op, a.shape if op != "fi_fwd_c2" else "8x256x448", a.flow, ma, mb, mb / ma, min(per_round[0]), max(per_round[0]),
+            min(per_round[1]), max(per_round[1]), a.libs[0], a.libs[1]), flush=True)
 
 
 if __name__ == "__main__":

@@ -13,6 +13,7 @@
 //         eight XCDs move down the same G * 8 strips together (a raster-compact front) and a tile's vertical neighbour
 //         is G positions later on the SAME XCD
 //      4  stripes two tile columns wide per XCD, row-major inside
+// and (round 7, skeleton_offset) the product's walk with the tile grid shifted left by 0 / 16 / 32 / 48 pixels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -310,6 +311,52 @@ extern "C" int probe_skeleton_phased(void *stream, int lx, int walk, int per, in
 #define GO(MODE) hipLaunchKernelGGL((skeleton_phased<16, MODE>), dim3(grid), dim3(256), 0, (hipStream_t)stream, W, H, (int64_t)W * H, \
                                     in1, flow, filt, out, tx, ty, walk, (unsigned)per, (unsigned)win)
     if (mode == 0) GO(0); else if (mode == 1) GO(1); else if (mode == 2) GO(2); else if (mode == 3) GO(3); else GO(4);
+#undef GO
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// TILE ORIGIN (round 7): the product's 64 x 16 tiles on its strip walk, every tile shifted left by XOFF pixels
+// (x0 = 64 * tx - XOFF) and the edge tiles laid out as the kernel would: ceil((W + XOFF) / 64) tile columns, the 18 stream
+// loads and the 3 own-pixel loads clamped into the row (xs = clamp(x, 0, W - 4)), lanes with x < 0 or x >= W masked at the
+// store.  At W = 1280 a row is 20 slots of 256 B and a 4 KiB period 16 of them: a 64-px tile row is one whole slot, so the
+// 16 rows x 21 planes of a workgroup fall on 4 slots of the period; XOFF = 32 splits every tile row into two 128-B halves of
+// two adjacent slots (8 per workgroup), XOFF = 16 / 48 into a 192 / 64-B pair.
+template <int XOFF>
+__global__ __launch_bounds__(256, 2) void skeleton_offset(int W, int H, int64_t plane, const float *__restrict__ in1,
+                                                          const float *__restrict__ flow, const float *__restrict__ filt,
+                                                          float *__restrict__ out, int tiles_x, int tiles_y)
+{
+    constexpr int LX = 16;
+    const Tile t = walk_tile(2, 0, blockIdx.x, gridDim.x, tiles_x, tiles_y);
+    const int b = t.b;
+    const int x = t.tx * 4 * LX - XOFF + 4 * (threadIdx.x % LX), y = t.ty * (256 / LX) + threadIdx.x / LX;
+    const bool inb = x >= 0 && x < W && y < H;
+    const int xs = min(max(x, 0), W - 4), ys = min(y, H - 1);
+    const int64_t o = (int64_t)ys * W + xs;
+    f32x4 acc = ldnt(flow + (b * 2 + 0) * plane + o) + ldnt(flow + (b * 2 + 1) * plane + o);
+    f32x4 tp[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) tp[k] = ldnt(filt + (b * 16 + k) * plane + o);
+    f32x4 im[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) im[c] = *reinterpret_cast<const f32x4 *>(in1 + (b * 3 + c) * plane + o);
+#pragma unroll
+    for (int k = 0; k < 16; k++) acc += tp[k];
+    if (!inb) return;
+#pragma unroll
+    for (int c = 0; c < 3; c++) stnt(out + (b * 3 + c) * plane + o, acc * im[c]);
+}
+
+extern "C" int probe_skeleton_offset(void *stream, int xoff, int B, int H, int W, const float *in1, const float *flow,
+                                     const float *filt, float *out)
+{
+    const int tx = (W + xoff + 63) / 64, ty = (H + 15) / 16;
+    const unsigned grid = (unsigned)tx * ty * B;
+    if (W % 4 || W < 4 || ((unsigned)tx * B) % 8) return -2;            // walk 2: whole strips per XCD
+#define GO(XOFF) hipLaunchKernelGGL((skeleton_offset<XOFF>), dim3(grid), dim3(256), 0, (hipStream_t)stream, W, H, (int64_t)W * H, \
+                                    in1, flow, filt, out, tx, ty)
+    if (xoff == 0) GO(0); else if (xoff == 16) GO(16); else if (xoff == 32) GO(32); else if (xoff == 48) GO(48);
+    else return -1;
 #undef GO
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -17,6 +17,8 @@ def main():
     if not torch.cuda.is_available():
         print("built", SO); return
     lib = ctypes.CDLL(SO)
+    if len(sys.argv) > 2 and sys.argv[2] == "offsets":
+        return offsets(lib, int(sys.argv[1]))
     dev = torch.device("cuda:0")
     B, H, W = 32, 720, 1280
     x = torch.rand(B, 3, H, W, device=dev); f = torch.randn(B, 2, H, W, device=dev)
@@ -158,6 +160,57 @@ def phased(lib, st, P, B, H, W, x, f, k, o, nbytes, rounds):
                 ("stores", "workgroup starts", "starts (stores half a period later)", "cached stores, L2 write-back requested",
                  "cached stores, no request (control):")[c[2]], c[1] / 100.0, c[0] / 100.0),
             t * 1e6, nbytes / t / 1e9, 100 * nbytes / t / 8e12), flush=True)
+
+
+def offsets(lib, rounds):
+    """the product's 64 x 16 tiles on its strip walk with the tile grid shifted left by 0 / 16 / 32 / 48 px (skeleton_offset), at
+    the headline shape and at 4K: every round times every offset (the order reversed on odd rounds), one median per offset and
+    round; the gate of the kernel change is offset 32 against offset 0 at 720p"""
+    dev = torch.device("cuda:0")
+    lib.probe_skeleton_offset.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 4
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    offs = (0, 32, 16, 48)
+    for B, H, W in ((32, 720, 1280), (8, 2160, 3840)):
+        x = torch.rand(B, 3, H, W, device=dev); f = torch.randn(B, 2, H, W, device=dev)
+        k = torch.rand(B, 16, H, W, device=dev); o = torch.zeros_like(x)
+        nbytes = B * H * W * 96
+        call = lambda xoff: lib.probe_skeleton_offset(st, xoff, B, H, W, x.data_ptr(), f.data_ptr(), k.data_ptr(), o.data_ptr())
+        ref = None
+        for xoff in offs:                                   # the shifted grids must store exactly what the plain one does
+            o.zero_()
+            assert call(xoff) == 0, xoff
+            torch.cuda.synchronize()
+            if ref is None:
+                ref = o.clone()
+            assert torch.equal(o, ref), "offset %d stores other values" % xoff
+        del ref
+        for _ in range(150):                                # the device's clocks (DESIGN.md section 4: ~100 launches)
+            call(0)
+        per_round = {c: [] for c in offs}
+        for r in range(rounds):
+            for xoff in (offs if r % 2 == 0 else offs[::-1]):
+                for _ in range(3):
+                    call(xoff)
+                ts = []
+                for _ in range(10):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(); call(xoff); b.record(); b.synchronize()
+                    ts.append(a.elapsed_time(b) * 1e-3)
+                per_round[xoff].append(statistics.median(ts))
+        base = statistics.median(per_round[0])
+        for xoff in offs:
+            v = per_round[xoff]
+            t = statistics.median(v)
+            print("%dx3x%dx%d  64x16 strips, tile grid -%2d px (%d tile columns)  median %8.1f us  rounds %8.1f .. %8.1f us  %6.3f  "
+                  "%5.1f%% of 8 TB/s" % (B, H, W, xoff, (W + xoff + 63) // 64, t * 1e6, min(v) * 1e6, max(v) * 1e6, t / base,
+                                         100 * nbytes / t / 8e12), flush=True)
+        print("%dx3x%dx%d  rounds of offset 0:  %s" % (B, H, W, " ".join("%.1f" % (s * 1e6) for s in per_round[0])))
+        print("%dx3x%dx%d  rounds of offset 32: %s" % (B, H, W, " ".join("%.1f" % (s * 1e6) for s in per_round[32])))
+        print("%dx3x%dx%d  gate (offset 32 >= 3 %% faster, ranges apart): %s" % (
+            B, H, W, "PASS" if statistics.median(per_round[32]) <= 0.97 * base and max(per_round[32]) < min(per_round[0]) else "FAIL"),
+            flush=True)
+        del x, f, k, o
+        torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":
