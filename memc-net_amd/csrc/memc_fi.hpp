@@ -2,6 +2,7 @@
 #pragma once
 
 #include "memc_tile.hpp"
+#include "memc_lp.hpp"
 
 namespace memc {
 
@@ -25,107 +26,163 @@ __device__ __forceinline__ unsigned fi_covered(const Region &r, const FiSite4 &g
 
 // Scalar evaluation of ONE site for channels [0, nch) of `plane0`, everything read from global memory
 // (flow, taps, image): the rare path for sites whose source window is not in the staged LDS region, and the
-// body of the any-filter-size kernel.  Same arithmetic order as the fast path.
-__device__ __forceinline__ float fi_quad_sum(const float *p, int s1h, int W, int H, const float *tap_p,
+// body of the any-filter-size kernel.  Same arithmetic order as the fast path.  P: the storage of the image and the taps
+// (memc_lp.hpp: F32, or F16 / BF16 widened exactly at the load).
+template <class P = F32>
+__device__ __forceinline__ float fi_quad_sum(const st_t<P> *p, int s1h, int W, int H, const st_t<P> *tap_p,
                                              int64_t s3c, int fs, int L, int T, int j0, int j1, int i0, int i1)
 {
     float acc = 0.0f;
     for (int j = j0; j <= j1; j++) {
         const int jj = clampi(j, H - 1) * s1h;
         for (int i = i0; i <= i1; i++)
-            acc += p[jj + clampi(i, W - 1)] * tap_p[((j - T) * fs + (i - L)) * s3c];
+            acc += widen_f32<P>(p[jj + clampi(i, W - 1)]) * widen_f32<P>(tap_p[((j - T) * fs + (i - L)) * s3c]);
     }
     return acc;
 }
 
+// The per-site backward helpers below are written once over the storage of their tensors (memc_lp.hpp): P for the image,
+// the taps and the tap gradient, FT for the flow and its gradient, GT for gradoutput; the image gradient is always fp32
+// (it takes atomics).  Every load widens exactly, every result is rounded once when it is stored: for the same (widened)
+// inputs a half instantiation computes the fp32 one's values.  The bodies are macros, expanded in the fp32 functions of
+// libmemc_hip.so (fi_bwd_site_scalar, fi_bwd_site_taps) and in the *_lp templates of libmemc_hip_lp_grad.so: a forwarding
+// call to a shared always-inline template would be the same source but not the same machine code (the inlined call
+// changes the compiler's vectorisation and contraction choices), and the fp32 kernels keep theirs bit for bit.
+
 // One site of the backward, everything from global memory, image gradient with global atomics: the rare path for
 // sites that no LDS band covers, and the body of the any-filter-size kernel (my_lib_kernel.cu:1248-1515).
+// The tap gradient is a sum over the channels: fp32 taps accumulate it in memory (g3[k] +=, exact in fp32); half taps
+// may not (each add would be rounded to T), so their sums are formed in a register from the same terms in the same
+// order, behind the channel loop, and stored once.
+#define MEMC_FI_BWD_SITE_SCALAR_BODY(P, FT, GT)                                                                       \
+    {                                                                                                                 \
+        constexpr bool kMem = sizeof(st_t<P>) == 4;                                                                   \
+        const float fx = widen_f32<FT>(flow_p[0]), fy = widen_f32<FT>(flow_p[s2c]);                                   \
+        const FiSite s = fi_locate(x, y, W, H, fx, fy);                                                               \
+        if (!s.valid) return;                                                                                         \
+        const int L = s.ix + 1 - fs / 2, T = s.iy + 1 - fs / 2, R = L + fs, Bm = T + fs;                              \
+        float botx = 0.0f, boty = 0.0f;                                                                               \
+        const float gam_x = 1.0f - s.b, gam_y = 1.0f - s.a;                                                           \
+        for (int c = 0; c < C; c++) {                                                                                 \
+            const st_t<P> *p = in_b + c * s1c;                                                                        \
+            float *q = gin1_b + c * s1c;                                                                              \
+            const float g = widen_f32<GT>(gout_p[c * s1c]);                                                           \
+            for (int j = T; j < Bm; j++) {                                                                            \
+                const int jj = clampi(j, H - 1) * s1h;                                                                \
+                for (int i = L; i < R; i++) {                                                                         \
+                    const int ii = clampi(i, W - 1);                                                                  \
+                    const float wgt = (j <= s.iy) ? ((i <= s.ix) ? g * (1 - s.a) * (1 - s.b) : g * s.a * (1 - s.b))   \
+                                                  : ((i <= s.ix) ? g * (1 - s.a) * s.b : g * s.a * s.b);              \
+                    const int64_t k = ((j - T) * fs + (i - L)) * s3c;                                                 \
+                    atomic_add_f32(q + jj + ii, wgt * widen_f32<P>(tap_p[k]));                                        \
+                    if constexpr (kMem) {                                                                             \
+                        if (c == 0) g3[k] = wgt * p[jj + ii]; else g3[k] += wgt * p[jj + ii];                         \
+                    }                                                                                                 \
+                }                                                                                                     \
+            }                                                                                                         \
+            const float TL = fi_quad_sum<P>(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, L, s.ix);                    \
+            const float TR = fi_quad_sum<P>(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, s.ix + 1, R - 1);            \
+            const float BL = fi_quad_sum<P>(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, L, s.ix);           \
+            const float BR = fi_quad_sum<P>(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, s.ix + 1, R - 1);   \
+            float tmp = 0.0f;                                                                                         \
+            tmp += gam_x * (TR - TL);                                                                                 \
+            tmp += (1.0f - gam_x) * (BR - BL);                                                                        \
+            botx += g * tmp;                                                                                          \
+            tmp = 0.0f;                                                                                               \
+            tmp += gam_y * (BL - TL);                                                                                 \
+            tmp += (1.0f - gam_y) * (BR - TR);                                                                        \
+            boty += g * tmp;                                                                                          \
+        }                                                                                                             \
+        if constexpr (!kMem) {   /* half taps: each tap's channel sum above, same terms, same order, in a register */ \
+            for (int j = T; j < Bm; j++) {                                                                            \
+                const int jj = clampi(j, H - 1) * s1h;                                                                \
+                for (int i = L; i < R; i++) {                                                                         \
+                    const int ii = clampi(i, W - 1);                                                                  \
+                    float a3 = 0.0f;                                                                                  \
+                    for (int c = 0; c < C; c++) {                                                                     \
+                        const float g = widen_f32<GT>(gout_p[c * s1c]);                                               \
+                        const float wgt = (j <= s.iy) ? ((i <= s.ix) ? g * (1 - s.a) * (1 - s.b) : g * s.a * (1 - s.b)) \
+                                                      : ((i <= s.ix) ? g * (1 - s.a) * s.b : g * s.a * s.b);          \
+                        const st_t<P> *p = in_b + c * s1c;                                                            \
+                        if (c == 0) a3 = wgt * widen_f32<P>(p[jj + ii]); else a3 += wgt * widen_f32<P>(p[jj + ii]);   \
+                    }                                                                                                 \
+                    g3[((j - T) * fs + (i - L)) * s3c] = narrow_f32<P>(a3);                                           \
+                }                                                                                                     \
+            }                                                                                                         \
+        }                                                                                                             \
+        g2[0] = narrow_f32<FT>(botx);                                                                                 \
+        g2[s2c] = narrow_f32<FT>(boty);                                                                               \
+    }
 __device__ __noinline__ inline void fi_bwd_site_scalar(int x, int y, int W, int H, int C, int fs,
                                                 const float *in_b, float *gin1_b, int64_t s1c, int s1h,
                                                 const float *flow_p, float *g2, int64_t s2c,
                                                 const float *tap_p, float *g3, int64_t s3c, const float *gout_p)
-{
-    const float fx = flow_p[0], fy = flow_p[s2c];
-    const FiSite s = fi_locate(x, y, W, H, fx, fy);
-    if (!s.valid) return;
-    const int L = s.ix + 1 - fs / 2, T = s.iy + 1 - fs / 2, R = L + fs, Bm = T + fs;
-    float botx = 0.0f, boty = 0.0f;
-    const float gam_x = 1.0f - s.b, gam_y = 1.0f - s.a;
-    for (int c = 0; c < C; c++) {
-        const float *p = in_b + c * s1c;
-        float *q = gin1_b + c * s1c;
-        const float g = gout_p[c * s1c];
-        for (int j = T; j < Bm; j++) {
-            const int jj = clampi(j, H - 1) * s1h;
-            for (int i = L; i < R; i++) {
-                const int ii = clampi(i, W - 1);
-                const float wgt = (j <= s.iy) ? ((i <= s.ix) ? g * (1 - s.a) * (1 - s.b) : g * s.a * (1 - s.b))
-                                              : ((i <= s.ix) ? g * (1 - s.a) * s.b : g * s.a * s.b);
-                const int64_t k = ((j - T) * fs + (i - L)) * s3c;
-                atomic_add_f32(q + jj + ii, wgt * tap_p[k]);
-                if (c == 0) g3[k] = wgt * p[jj + ii]; else g3[k] += wgt * p[jj + ii];
-            }
-        }
-        const float TL = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, L, s.ix);
-        const float TR = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, s.ix + 1, R - 1);
-        const float BL = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, L, s.ix);
-        const float BR = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, s.ix + 1, R - 1);
-        float tmp = 0.0f;
-        tmp += gam_x * (TR - TL);
-        tmp += (1.0f - gam_x) * (BR - BL);
-        botx += g * tmp;
-        tmp = 0.0f;
-        tmp += gam_y * (BL - TL);
-        tmp += (1.0f - gam_y) * (BR - TR);
-        boty += g * tmp;
-    }
-    g2[0] = botx;
-    g2[s2c] = boty;
-}
+MEMC_FI_BWD_SITE_SCALAR_BODY(F32, F32, F32)
+template <class P, class FT, class GT>
+__device__ __noinline__ void fi_bwd_site_scalar_lp(int x, int y, int W, int H, int C, int fs, const st_t<P> *in_b,
+                                                   float *gin1_b, int64_t s1c, int s1h, const st_t<FT> *flow_p,
+                                                   st_t<FT> *g2, int64_t s2c, const st_t<P> *tap_p, st_t<P> *g3,
+                                                   int64_t s3c, const st_t<GT> *gout_p)
+MEMC_FI_BWD_SITE_SCALAR_BODY(P, FT, GT)
+#undef MEMC_FI_BWD_SITE_SCALAR_BODY
 
 
 // gradinput3 and gradinput2 of ONE site straight from global memory (mixed quads of the tiled RGB backward: some of a
 // lane's four sites belong to another band or are invalid).  Assigns both, like the tiled path; the image
 // gradient of such a site still goes through the tile's LDS planes.
+#define MEMC_FI_BWD_SITE_TAPS_BODY(P, FT, GT)                                                                         \
+    {                                                                                                                 \
+        const FiSite s = fi_locate(x, y, W, H, widen_f32<FT>(flow_p[0]), widen_f32<FT>(flow_p[s2c]));                 \
+        if (!s.valid) return;                                                                                         \
+        const float g0 = widen_f32<GT>(gout_p[0]), g1 = widen_f32<GT>(gout_p[s1c]), gc2 = widen_f32<GT>(gout_p[2 * s1c]); \
+        float gx = 0.0f, gy = 0.0f;                                                                                   \
+        for (int k = 0; k < 4; k++) {                                                                                 \
+            const st_t<P> *row = in_b + (int64_t)clampi(s.iy - 1 + k, H - 1) * s1h;                                   \
+            for (int m = 0; m < 4; m++) {                                                                             \
+                const st_t<P> *p = row + clampi(s.ix - 1 + m, W - 1);                                                 \
+                float sv = 0.0f;                                                                                      \
+                sv += g0 * widen_f32<P>(p[0]);  sv += g1 * widen_f32<P>(p[s1c]);  sv += gc2 * widen_f32<P>(p[2 * s1c]); \
+                const float wa = m < 2 ? (1 - s.a) : s.a, wb = k < 2 ? (1 - s.b) : s.b;                               \
+                g3[(k * 4 + m) * s3c] = narrow_f32<P>((wa * wb) * sv);                                                \
+                const float st = sv * widen_f32<P>(tap_p[(k * 4 + m) * s3c]);                                         \
+                gx += (m < 2 ? -wb : wb) * st;                                                                        \
+                gy += (k < 2 ? -wa : wa) * st;                                                                        \
+            }                                                                                                         \
+        }                                                                                                             \
+        g2[0] = narrow_f32<FT>(gx);                                                                                   \
+        g2[s2c] = narrow_f32<FT>(gy);                                                                                 \
+    }
 __device__ __noinline__ inline void fi_bwd_site_taps(int x, int y, int W, int H, const float *in_b, int64_t s1c, int s1h,
                                               const float *flow_p, float *g2, int64_t s2c, const float *tap_p,
                                               float *g3, int64_t s3c, const float *gout_p)
-{
-    const FiSite s = fi_locate(x, y, W, H, flow_p[0], flow_p[s2c]);
-    if (!s.valid) return;
-    const float g0 = gout_p[0], g1 = gout_p[s1c], gc2 = gout_p[2 * s1c];
-    float gx = 0.0f, gy = 0.0f;
-    for (int k = 0; k < 4; k++) {
-        const float *row = in_b + (int64_t)clampi(s.iy - 1 + k, H - 1) * s1h;
-        for (int m = 0; m < 4; m++) {
-            const float *p = row + clampi(s.ix - 1 + m, W - 1);
-            float sv = 0.0f;
-            sv += g0 * p[0];  sv += g1 * p[s1c];  sv += gc2 * p[2 * s1c];
-            const float wa = m < 2 ? (1 - s.a) : s.a, wb = k < 2 ? (1 - s.b) : s.b;
-            g3[(k * 4 + m) * s3c] = (wa * wb) * sv;
-            const float st = sv * tap_p[(k * 4 + m) * s3c];
-            gx += (m < 2 ? -wb : wb) * st;
-            gy += (k < 2 ? -wa : wa) * st;
-        }
-    }
-    g2[0] = gx;
-    g2[s2c] = gy;
-}
+MEMC_FI_BWD_SITE_TAPS_BODY(F32, F32, F32)
+template <class P, class FT, class GT>
+__device__ __noinline__ void fi_bwd_site_taps_lp(int x, int y, int W, int H, const st_t<P> *in_b, int64_t s1c, int s1h,
+                                                 const st_t<FT> *flow_p, st_t<FT> *g2, int64_t s2c, const st_t<P> *tap_p,
+                                                 st_t<P> *g3, int64_t s3c, const st_t<GT> *gout_p)
+MEMC_FI_BWD_SITE_TAPS_BODY(P, FT, GT)
+#undef MEMC_FI_BWD_SITE_TAPS_BODY
 
 // gradinput2 / gradinput3 are fully DEFINED by the backward kernels (the Python layer hands them over
 // uninitialised -- their memsets were 72 B/site, a seventh of the call): a quad that contains an invalid site
 // first stores zeros to its 16 + 2 float4; its valid sites are then stored site by site (fi_bwd_site_taps), by the
 // same lane and therefore after these.  Quads of four valid sites are stored by phase 1 or by fi_bwd_site_taps.
-__device__ __forceinline__ void fi_bwd_zero_invalid(bool inb, unsigned valid, float *gin2_b, int64_t s2c, unsigned o2,
-                                                    float *gin3_b, int64_t s3c, unsigned o3)
+// (o2 / o3: byte offsets; a half quad is 8 bytes, 8-byte aligned.)
+template <class P = F32, class FT = F32>
+__device__ __forceinline__ void fi_bwd_zero_invalid(bool inb, unsigned valid, st_t<FT> *gin2_b, int64_t s2c, unsigned o2,
+                                                    st_t<P> *gin3_b, int64_t s3c, unsigned o3)
 {
     if (!inb || valid == 0xFu) return;         // rare (image borders, |flow| guard): ordinary 64-bit addressing
-    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    float *q3 = gin3_b + (o3 >> 2), *q2 = gin2_b + (o2 >> 2);
+    st_t<P> *q3 = gin3_b + (o3 / (unsigned)sizeof(st_t<P>));
+    st_t<FT> *q2 = gin2_b + (o2 / (unsigned)sizeof(st_t<FT>));
+    auto zero4 = [](auto *q) {
+        if constexpr (sizeof(*q) == 4) *reinterpret_cast<f32x4u *>(q) = f32x4{0.f, 0.f, 0.f, 0.f};
+        else *reinterpret_cast<u16x4a *>(q) = u16x4{0, 0, 0, 0};
+    };
 #pragma unroll 1
-    for (int k = 0; k < 16; k++) *reinterpret_cast<f32x4u *>(q3 + k * s3c) = z;
-    *reinterpret_cast<f32x4u *>(q2) = z;
-    *reinterpret_cast<f32x4u *>(q2 + s2c) = z;
+    for (int k = 0; k < 16; k++) zero4(q3 + k * s3c);
+    zero4(q2);
+    zero4(q2 + s2c);
 }
 
 }  // namespace memc

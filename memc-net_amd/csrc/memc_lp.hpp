@@ -1,4 +1,5 @@
-// memc_lp.hpp -- half-width storage for the adaptive-warp forward of libmemc_hip_lp.so (lp_filter_interpolation.hip).
+// memc_lp.hpp -- half-width storage for the adaptive-warp forward of libmemc_hip_lp.so (lp_filter_interpolation.hip) and
+// the RGB backward of libmemc_hip_lp_grad.so (lp_fi_bwd_c3.hip, memc_fi_bwd_c3.hpp).
 //
 // Numerics contract (include/memc_warp_lp.h):
 //   * payload type T in {fp16, bf16}: the image / features, the filter taps, the occlusions (blend) and the output;
@@ -15,6 +16,8 @@
 #pragma once
 
 #include "memc_tile.hpp"
+
+#include <type_traits>
 
 namespace memc {
 
@@ -54,6 +57,37 @@ template <> __device__ __forceinline__ unsigned short narrow<BF16>(float v)
     return __builtin_bit_cast(unsigned short, (__bf16)v);
 }
 
+// fp32 -> T of a value that the fp32 kernels round to fp32 first (the backward of libmemc_hip_lp_grad.so).  For fp16 the
+// empty asm keeps the compiler from folding the multiply or FMA that produced `v` into the conversion: v_fma_mixlo_f16
+// rounds the exact result to fp16 once -- not the fp32 value, so an fp32 value that is an fp16 tie can round the other
+// way (seen: one tap gradient in ~2000).  bf16 has no such fused form.
+template <class S>
+__device__ __forceinline__ st_t<S> narrow_f32(float v)
+{
+    if constexpr (std::is_same_v<S, F16>) asm volatile("" : "+v"(v));
+    return narrow<S>(v);
+}
+
+// T -> fp32 as an opaque value (the per-site backward helpers, memc_fi.hpp): the compiler then sees an fp32 operand, as it
+// does in the fp32 kernels, and cannot fold the conversion into a mixed-precision FMA (v_fma_mix_f32) -- which would fuse
+// a multiply and an add that the fp32 code keeps apart, or keep apart ones it fuses (its vectoriser chooses differently).
+template <class S>
+__device__ __forceinline__ float widen_f32(st_t<S> v)
+{
+    float f = widen<S>(v);
+    if constexpr (!std::is_same_v<S, F32>) asm volatile("" : "+v"(f));
+    return f;
+}
+
+// a widened fp16 quad made opaque (the flow of the RGB backward): with the conversions in view the compiler vectorises the
+// arithmetic that follows differently from the fp32 kernel's (other multiplies and adds end up fused); F32 / BF16: as is
+template <class S>
+__device__ __forceinline__ f32x4 opaque4(f32x4 v)
+{
+    if constexpr (std::is_same_v<S, F16>) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
+    return v;
+}
+
 template <class S>
 __device__ __forceinline__ f32x4 widen4(const u16x4 &q)
 {
@@ -79,6 +113,27 @@ __device__ __forceinline__ void st4_stream(st_t<S> *p, const f32x4 &v)
 {
     const u16x4 q = {narrow<S>(v[0]), narrow<S>(v[1]), narrow<S>(v[2]), narrow<S>(v[3])};
     __builtin_nontemporal_store(q, reinterpret_cast<u16x4a *>(p));
+}
+// the same through wave-uniform base + 32-bit byte offset (ld_stream4_u / st_stream4_u of memc_tile.hpp; F32: those exactly);
+// the store rounds fp32 values (see narrow_f32)
+template <class S>
+__device__ __forceinline__ f32x4 ld4_stream_u(const st_t<S> *ubase, unsigned byte_off)
+{
+    if constexpr (sizeof(st_t<S>) == 4) return ld_stream4_u(ubase, byte_off);
+    else return widen4<S>(__builtin_nontemporal_load(reinterpret_cast<const MEMC_GLOBAL u16x4a *>(addr_u(ubase, byte_off))));
+}
+template <class S>
+__device__ __forceinline__ void st4_stream_u(st_t<S> *ubase, unsigned byte_off, f32x4 v)
+{
+    if constexpr (sizeof(st_t<S>) == 4) {
+        st_stream4_u(ubase, byte_off, v);
+    } else {
+        // the quad as a whole is the asm's operand: the compiler still sees one fp32 vector consumed, as by the fp32
+        // store, and vectorises what computes it the same way (four scalar consumers -- narrow_f32 -- fuse differently)
+        asm volatile("" : "+v"(v));
+        const u16x4 q = {narrow<S>(v[0]), narrow<S>(v[1]), narrow<S>(v[2]), narrow<S>(v[3])};
+        __builtin_nontemporal_store(q, reinterpret_cast<MEMC_GLOBAL u16x4a *>(addr_u(ubase, byte_off)));
+    }
 }
 
 // Staging of NCH (1..4) T planes into the fp32 pixel-quad LDS image of memc_tile.hpp: the same slots and the same

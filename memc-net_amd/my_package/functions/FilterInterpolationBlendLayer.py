@@ -12,9 +12,12 @@ composed from FilterInterpolationLayer calls -- same values, no error.
 
 float16 / bfloat16 (functions/_common.py: payload_dtype): the payload dtype is torch.promote_types over the images, the
 taps and the occlusions, which are cast to it; the flows stay float32 or that dtype.  The forward is one kernel of
-libmemc_hip_lp.so for every shape (fp32 arithmetic, one rounding of the blended value).  The BACKWARD of a half call is
-not accelerated: the saved inputs are widened to float32, the float32 path above computes the gradients, and each comes
-back in its input's dtype.
+libmemc_hip_lp.so for every shape (fp32 arithmetic, one rounding of the blended value).  The backward of a half call
+recomputes both warps and the occlusion gradients in float32 on the widened inputs, as the float32 path does; its two
+per-direction backward launches run on the half kernel of libmemc_hip_lp_grad.so wherever it covers the direction (RGB,
+16 taps, width a multiple of four), on the half image and taps, with the float32 gradoutput * occlusion (exact: a product
+of two widened halves).  Elsewhere they run the float32 kernel on the widened inputs.  Each gradient comes back in its
+input's dtype.
 """
 import torch
 from torch.autograd import Function
@@ -23,7 +26,7 @@ from torch.autograd.function import once_differentiable
 import my_package._ext.my_lib as my_lib
 import my_package._ext.my_lib_lp as my_lib_lp
 from ._common import cast, check, f32c, flow_dtype, payload_dtype, require_gpu
-from .FilterInterpolationLayer import FilterInterpolationLayer
+from .FilterInterpolationLayer import FilterInterpolationLayer, backward_lp, lp_backward_covered
 
 
 def fused_supported(input0, filter0, *others):
@@ -44,18 +47,27 @@ def _warp(x, flow, filt):
     return out
 
 
-def _blend_backward(saved, gradoutput):
+def _blend_backward(saved, gradoutput, half=None):
     """gradients of occ0 * FI(in0, flow0, filt0) + occ1 * FI(in2, flow1, filt1) w.r.t. its eight inputs, through the
-    reference-API entry points (two forward recomputations + two backward launches)"""
+    reference-API entry points (two forward recomputations + two backward launches).  half: the float16 / bfloat16
+    tensors that `saved` widens -- each direction's backward launch then runs on them (libmemc_hip_lp_grad.so) where the
+    library covers it; its flow / tap gradients come back in their dtypes, the image gradient in float32."""
     input0, input2, flow0, flow1, filter0, filter1, occ0, occ1 = saved
     grads = []
-    for x, flow, filt, occ in ((input0, flow0, filter0, occ0), (input2, flow1, filter1, occ1)):
+    for d, (x, flow, filt, occ) in enumerate(((input0, flow0, filter0, occ0), (input2, flow1, filter1, occ1))):
         warped = _warp(x, flow, filt)                        # recomputed, not stored by the forward pass
         g_occ = (gradoutput * warped).sum(dim=1, keepdim=True)
         g_warp = (gradoutput * occ).contiguous()
-        g_x, g_flow, g_filt = torch.zeros_like(x), torch.empty_like(flow), torch.empty_like(filt)
-        check(my_lib.FilterInterpolationLayer_gpu_backward(x, flow, filt, g_warp, g_x, g_flow, g_filt),
-              "FilterInterpolationLayer_gpu_backward")
+        g_x = torch.zeros_like(x)
+        g_lp = None
+        if half is not None and lp_backward_covered(half[d], half[4 + d]):
+            g_lp = backward_lp(half[d], half[2 + d], half[4 + d], g_warp, g_x)
+        if g_lp is not None:
+            g_flow, g_filt = g_lp
+        else:
+            g_flow, g_filt = torch.empty_like(flow), torch.empty_like(filt)
+            check(my_lib.FilterInterpolationLayer_gpu_backward(x, flow, filt, g_warp, g_x, g_flow, g_filt),
+                  "FilterInterpolationLayer_gpu_backward")
         grads.append((g_x, g_flow, g_filt, g_occ))
     (gx0, gf0, gk0, go0), (gx2, gf1, gk1, go1) = grads
     return gx0, gx2, gf0, gf1, gk0, gk1, go0, go1
@@ -80,7 +92,8 @@ class _FilterInterpolationBlendFunction(Function):
 
 
 class _FilterInterpolationBlendLpFunction(Function):
-    """float16 / bfloat16: forward on libmemc_hip_lp.so; backward widened to float32 (not accelerated)"""
+    """float16 / bfloat16: forward on libmemc_hip_lp.so; backward: float32 recomputation of the warps and occlusion
+    gradients, the two warp backward launches on libmemc_hip_lp_grad.so where it covers them"""
 
     @staticmethod
     def forward(ctx, input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):
@@ -95,7 +108,7 @@ class _FilterInterpolationBlendLpFunction(Function):
     @once_differentiable
     def backward(ctx, gradoutput):
         saved = ctx.saved_tensors
-        grads = _blend_backward(tuple(t.float().contiguous() for t in saved), gradoutput.float().contiguous())
+        grads = _blend_backward(tuple(t.float().contiguous() for t in saved), gradoutput.float().contiguous(), half=saved)
         return tuple(g.to(t.dtype) for g, t in zip(grads, saved))
 
 

@@ -13,8 +13,11 @@ Differences, all deliberate:
   * CPU tensors raise (the reference's CPU branch dies with NameError);
   * float16 / bfloat16 (functions/_common.py: payload_dtype): the payload dtype of a call is torch.promote_types over
     input1 and input3, which are cast to it; the flow stays float32 or that dtype.  The forward runs on the half kernels
-    of libmemc_hip_lp.so and returns that dtype.  The BACKWARD of a half call is not accelerated: it widens the saved
-    inputs to float32, runs the float32 backward kernels and returns each gradient in its input's dtype.
+    of libmemc_hip_lp.so and returns that dtype.  The backward of a half call with three channels, the 4x4 filter and a
+    width that is a multiple of four (from 8 on) runs on the half kernel of libmemc_hip_lp_grad.so: the same arithmetic
+    as the float32 backward on the widened inputs, each flow / tap gradient rounded once, the image gradient an fp32
+    buffer rounded afterwards.  Any other half call widens the saved inputs to float32, runs the float32 backward
+    kernels and returns each gradient in its input's dtype.
 """
 import torch
 from torch.autograd import Function
@@ -22,6 +25,7 @@ from torch.autograd.function import once_differentiable
 
 import my_package._ext.my_lib as my_lib
 import my_package._ext.my_lib_lp as my_lib_lp
+import my_package._ext.my_lib_lp_grad as my_lib_lp_grad
 from ._common import cast, check, f32c, flow_dtype, payload_dtype, require_gpu
 
 
@@ -78,8 +82,45 @@ def _backward_fp32(input1, input2, input3, gradoutput, want1):
     return (gradinput1 if want1 else None), gradinput2, gradinput3
 
 
+def lp_backward_covered(input1, input3):
+    """What libmemc_hip_lp_grad.so's kernel takes (include/memc_warp_lp_grad.h): three channels, 16 taps, a width that is a
+    multiple of four from 8 on.  (Views it declines all the same -- misaligned, say -- come back as return code 1.)"""
+    return input1.size(1) == 3 and input3.size(1) == 16 and input1.size(3) % 4 == 0 and input1.size(3) >= 8
+
+
+def backward_lp(input1, input2, input3, gradoutput, gradinput1):
+    """(gradinput2, gradinput3) of half input1 / input3 on libmemc_hip_lp_grad.so, gradinput1 (None or float32, zero-filled)
+    added into; None where the library does not cover the call (return code 1: nothing was touched)"""
+    gradinput2 = torch.empty_like(input2)                # every element is written (invalid sites store zero)
+    gradinput3 = torch.empty_like(input3)
+    err = my_lib_lp_grad.FilterInterpolationLayer_gpu_backward_lp(
+        input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3)
+    if err == 1:
+        return None
+    check(err, "FilterInterpolationLayer_gpu_backward_lp")
+    return gradinput2, gradinput3
+
+
+def _backward_lp(input1, input2, input3, gradoutput, want1):
+    """_backward_fp32 on half tensors: the same gradinput1 decision (so the kernel takes the float32 library's PART for the
+    call), gradinput1 float32; None where the library does not cover the call"""
+    null_ok = input1.size(1) == 3 and input3.size(1) == 16 and input1.size(3) % 4 == 0
+    if want1 or not null_ok:
+        stored = my_lib.gradinput1_is_stored(int(input3.size(1) ** 0.5 + 1e-6), input1.size(1))
+        gradinput1 = (torch.empty_like if stored else torch.zeros_like)(input1, dtype=torch.float32)
+    else:
+        gradinput1 = None
+    if gradoutput.dtype not in (input1.dtype, torch.float32):
+        gradoutput = gradoutput.float()
+    grads = backward_lp(input1, input2, input3, gradoutput.contiguous(), gradinput1)
+    if grads is None:
+        return None
+    return (gradinput1 if want1 else None,) + grads
+
+
 class _FilterInterpolationLpFunction(Function):
-    """float16 / bfloat16: forward on libmemc_hip_lp.so; backward widened to float32 (not accelerated)"""
+    """float16 / bfloat16: forward on libmemc_hip_lp.so; backward on libmemc_hip_lp_grad.so where it covers the call, else
+    widened to float32"""
 
     @staticmethod
     def forward(ctx, input1, input2, input3):
@@ -94,8 +135,12 @@ class _FilterInterpolationLpFunction(Function):
     @once_differentiable
     def backward(ctx, gradoutput):
         saved = ctx.saved_tensors
-        input1, input2, input3 = (t.float().contiguous() for t in saved)
-        grads = _backward_fp32(input1, input2, input3, gradoutput.float().contiguous(), ctx.needs_input_grad[0])
+        grads = None
+        if lp_backward_covered(saved[0], saved[2]):
+            grads = _backward_lp(*saved, gradoutput, ctx.needs_input_grad[0])
+        if grads is None:                                    # widened: the float32 kernels
+            input1, input2, input3 = (t.float().contiguous() for t in saved)
+            grads = _backward_fp32(input1, input2, input3, gradoutput.float().contiguous(), ctx.needs_input_grad[0])
         return tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, saved))
 
 

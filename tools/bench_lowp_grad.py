@@ -1,0 +1,149 @@
+#!/usr/bin/env python
+"""tools/bench_lowp_grad.py -- the half-precision adaptive-warp backward: the widened route against the native kernel, in
+one process.
+
+    python tools/bench_lowp_grad.py [--rounds 7] [--iters 10] [--only SUBSTRING] [--json out.json]
+
+The widened route is what every half backward took before libmemc_hip_lp_grad.so, and what uncovered shapes still take
+(FilterInterpolationLayer._backward_fp32 on the inputs cast to float32, each gradient cast back; for the blend,
+_blend_backward on the widened inputs).  The native route is the code the autograd Functions now run (_backward_lp;
+_blend_backward with the half tensors).  Both are timed as whole backward passes, casts and allocations included,
+ALTERNATELY, round after round, so that clock and thermal drift fall on both alike; each launch rotates over input sets
+that together exceed the 256 MiB Infinity Cache several times.  Printed per row: the per-round medians of both routes,
+the median over the rounds, the spread (max - min over the rounds, relative to the median) and the ratio."""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "memc-net_amd")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+from tools.bench_ops import time_launches      # noqa: E402
+from tools import synth                        # noqa: E402
+
+ROTATE_BYTES = 1 << 30
+
+
+def _sets(shape, n, blend, T, half_flow, seed):
+    B, C, H, W = shape
+    ft = T if half_flow else torch.float32
+    out = []
+    for i in range(n):
+        t = synth.torch_inputs("cuda", B, C, H, W, flow_kind="smooth", seed=seed + 97 * i)
+        g = torch.Generator("cuda").manual_seed(seed + i)
+        s = {"x": t["x"].to(T), "flow": t["flow"].to(ft), "filt": t["filt"].to(T),
+             "gout": torch.randn(B, C, H, W, device="cuda", generator=g).to(T)}
+        if blend:
+            u = synth.torch_inputs("cuda", B, C, H, W, flow_kind="smooth", seed=seed + 97 * i + 1)
+            o = torch.rand(B, 1, H, W, device="cuda", generator=g)
+            s.update(x2=u["x"].to(T), flow2=u["flow"].to(ft), filt2=u["filt"].to(T), occ0=o.to(T), occ1=(1 - o).to(T))
+        out.append(s)
+    return out
+
+
+def _callers(op, sets, want1):
+    from my_package.functions import FilterInterpolationLayer as FL
+    from my_package.functions import FilterInterpolationBlendLayer as BL
+    state = {"i": 0}
+
+    def pick():
+        i = state["i"]
+        state["i"] = (i + 1) % len(sets)
+        return sets[i]
+
+    if op == "fi":
+        def widened():
+            s = pick()
+            saved = (s["x"], s["flow"], s["filt"])
+            x, flow, filt = (t.float().contiguous() for t in saved)
+            grads = FL._backward_fp32(x, flow, filt, s["gout"].float().contiguous(), want1)
+            return tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, saved))
+
+        def native():
+            s = pick()
+            saved = (s["x"], s["flow"], s["filt"])
+            grads = FL._backward_lp(*saved, s["gout"], want1)
+            assert grads is not None, "not covered"
+            return tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, saved))
+    else:
+        def _blend(half):
+            s = pick()
+            saved = tuple(s[k] for k in ("x", "x2", "flow", "flow2", "filt", "filt2", "occ0", "occ1"))
+            wide = tuple(t.float().contiguous() for t in saved)
+            grads = BL._blend_backward(wide, s["gout"].float().contiguous(), half=saved if half else None)
+            return tuple(g.to(t.dtype) for g, t in zip(grads, saved))
+
+        def widened():
+            return _blend(False)
+
+        def native():
+            return _blend(True)
+    return {"widened": widened, "native": native}
+
+
+def run_case(name, op, shape, T, half_flow, want1, rounds, iters):
+    B, C, H, W = shape
+    per_set = B * H * W * (2 * C + 16 + 2 * 4) * (2 if op == "blend" else 1) * 2        # half bytes, roughly
+    n = max(2, math.ceil(ROTATE_BYTES / per_set))
+    sets = _sets(shape, n, op == "blend", T, half_flow, seed=2468)
+    calls = _callers(op, sets, want1)
+    times = {"widened": [], "native": []}
+    for _ in range(rounds):
+        for route in ("widened", "native"):
+            med, _mn = time_launches(calls[route], warmup=2, iters=iters)
+            times[route].append(med)
+    row = {"case": name, "rounds": rounds, "iters": iters, "input_sets": n}
+    for route in ("widened", "native"):
+        ts = times[route]
+        m = statistics.median(ts)
+        row[route + "_us_per_round"] = [round(t * 1e6, 1) for t in ts]
+        row[route + "_us"] = round(m * 1e6, 1)
+        row[route + "_spread"] = round((max(ts) - min(ts)) / m, 4)
+    row["ratio"] = round(row["native_us"] / row["widened_us"], 3)
+    del sets, calls
+    torch.cuda.empty_cache()
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--only", default=None, help="run the cases whose name contains this string")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    big = (32, 3, 720, 1280)
+    cases = []
+    for tname, T in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
+        for half_flow in (False, True):
+            for want1 in (True, False):
+                cases.append(("fi_bwd %s 32x3x720x1280 %s flow %s" % (tname, "T" if half_flow else "fp32",
+                                                                      "image" if want1 else "noimage"),
+                              "fi", big, T, half_flow, want1))
+    cases.append(("fi_bwd bf16 8x3x256x448 fp32 flow noimage", "fi", (8, 3, 256, 448), torch.bfloat16, False, False))
+    cases.append(("fi_bwd bf16 8x3x256x448 fp32 flow image", "fi", (8, 3, 256, 448), torch.bfloat16, False, True))
+    cases.append(("blend_bwd bf16 32x3x720x1280 fp32 flow", "blend", big, torch.bfloat16, False, True))
+    rows = []
+    for name, op, shape, T, half_flow, want1 in cases:
+        if a.only and a.only not in name:
+            continue
+        r = run_case(name, op, shape, T, half_flow, want1, a.rounds, a.iters)
+        rows.append(r)
+        print("%-44s widened %9.1f us (spread %5.1f%%)  native %9.1f us (spread %5.1f%%)  x%.3f" % (
+            r["case"], r["widened_us"], 100 * r["widened_spread"], r["native_us"], 100 * r["native_spread"], r["ratio"]))
+        print("    per round  widened %s" % r["widened_us_per_round"])
+        print("               native  %s" % r["native_us_per_round"], flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
