@@ -104,7 +104,13 @@ __device__ __forceinline__ float fi_quad_sum(const st_t<P> *p, int s1h, int W, i
                         const float wgt = (j <= s.iy) ? ((i <= s.ix) ? g * (1 - s.a) * (1 - s.b) : g * s.a * (1 - s.b)) \
                                                       : ((i <= s.ix) ? g * (1 - s.a) * s.b : g * s.a * s.b);          \
                         const st_t<P> *p = in_b + c * s1c;                                                            \
-                        if (c == 0) a3 = wgt * widen_f32<P>(p[jj + ii]); else a3 += wgt * widen_f32<P>(p[jj + ii]);   \
+                        /* the fp32 function's `g3[k] += wgt * p` is a rounded product and an add (v_mul, v_add: its */ \
+                        /* store of channel 0 sits between them); here the loop unrolls and the compiler would       */ \
+                        /* contract the adds into fmas -- a last-bit difference that flips about one rounding to T   */ \
+                        /* in 2^13.  The asm keeps the product a value of its own.                                   */ \
+                        float t3 = wgt * widen_f32<P>(p[jj + ii]);                                                    \
+                        asm volatile("" : "+v"(t3));                                                                  \
+                        if (c == 0) a3 = t3; else a3 += t3;                                                           \
                     }                                                                                                 \
                     g3[((j - T) * fs + (i - L)) * s3c] = narrow_f32<P>(a3);                                           \
                 }                                                                                                     \

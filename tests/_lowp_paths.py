@@ -1,0 +1,140 @@
+"""tests/_lowp_paths.py -- which in-kernel path of the tiled fp16 / bf16 warps an input runs, counted on the CPU.
+
+libmemc_hip_lp.so and libmemc_hip_lp_grad.so report only the kernel family of a call (last_kernel_path()); whether a tile
+swept several LDS bands, hit the kMaxBands cap, sent sites to the per-site loop from global memory or stored a lane's four
+sites in pieces is decided inside the kernel.  This module restates that decision in numpy (memc-net_amd/csrc: fi_locate
+of memc_common.hpp; TileGeom<16>, tile_bbox, make_bands<16, true, 3072>, band_region of memc_tile.hpp; fi_covered of
+memc_fi.hpp; the `done` bookkeeping of fi_fwd_lp_tiled, fi_blend_lp_tiled and fi_bwd_c3_body.inc, which all three share)
+so that a test can state which paths its inputs reach.  tests/test_lowp_path_census.py holds the constants below to the
+header's text and the case table to its conditions; tests/test_gpu_lowp_paths.py runs the table on the GPU.
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "memc-net_amd")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+from tools import synth      # noqa: E402
+
+# geometry the census assumes (test_lowp_path_census.py reads the same values out of memc_tile.hpp)
+LX = 16                      # lanes per tile row
+TW, TH = 4 * LX, 256 // LX   # 64 x 16 sites per tile, four consecutive sites of a row per lane
+PITCH = TW + 32              # kPitch
+CAP = 3072                   # LDS budget in pixel quads
+MAX_BANDS = 6                # kMaxBands
+STEP_X = (PITCH - 4) & ~3    # 92: bands overlap by four columns
+
+# (B, H, W, flow kind, sigma, seed): the flow is the FIRST draw from np.random.default_rng(seed)
+CASES = [
+    (1, 96, 256, "smooth", 25.0, 16),      # bands in both directions, one capped tile, a handful of slow sites
+    (2, 64, 256, "iid", 20.0, 8),          # every tile sweeps the full six bands, nothing slow, thousands of split lanes
+    (1, 112, 320, "iid", 30.0, 22),        # most tiles capped: thousands of slow sites
+    (1, 200, 320, "smooth", 40.0, 23),     # capped tiles under smooth motion; a ragged last tile row (200 = 12 * 16 + 8)
+    (2, 100, 132, "smooth", 8.0, 12),      # tiles without a valid site; 4-column edge tiles (132 = 2 * 64 + 4)
+    (1, 40, 40, "iid", 30.0, 6),           # three partial tiles, mostly invalid sites, lanes of mixed validity
+]
+CASE_IDS = ["%dx%dx%d-%s%g" % c[:5] for c in CASES]
+BLEND_CASES = CASES[:4]                    # the second direction's flow: the first draw from seed + 100
+
+
+def case_flow(case, second=False):
+    B, H, W, kind, sigma, seed = case
+    return synth.np_flow(np.random.default_rng(seed + (100 if second else 0)), B, H, W, kind, sigma)
+
+
+def case_inputs(case, C, signed_gradient=True):
+    """(image, flow, taps, gradoutput) of a table case: the flow first, then the rest from the same generator"""
+    B, H, W, kind, sigma, seed = case
+    rng = np.random.default_rng(seed)
+    flow = synth.np_flow(rng, B, H, W, kind, sigma)
+    x, filt = synth.np_image(rng, B, C, H, W), synth.np_filter(rng, B, H, W)
+    gout = rng.standard_normal((B, C, H, W)).astype(np.float32) if signed_gradient else synth.np_image(rng, B, C, H, W)
+    return x, flow, filt, gout
+
+
+def rounded(a, tname):
+    """a (fp32 numpy) rounded to fp16 / bf16 and widened again; "fp32": unchanged"""
+    if tname == "fp32":
+        return np.ascontiguousarray(a, dtype=np.float32)
+    import torch
+    T = {"fp16": torch.float16, "bf16": torch.bfloat16}[tname]
+    return torch.from_numpy(np.ascontiguousarray(a)).to(T).float().numpy()
+
+
+def locate(flow):
+    """fi_locate for every site, in float32 as the kernels compute it: (valid, ix, iy)"""
+    B, _, H, W = flow.shape
+    fx, fy = flow[:, 0].astype(np.float32), flow[:, 1].astype(np.float32)
+    x2 = np.arange(W, dtype=np.float32)[None, None, :] + fx
+    y2 = np.arange(H, dtype=np.float32)[None, :, None] + fy
+    valid = ((x2 >= 0) & (y2 >= 0) & (x2 <= np.float32(W - 1)) & (y2 <= np.float32(H - 1)) &
+             (np.abs(fx) < np.float32(W) / np.float32(2)) & (np.abs(fy) < np.float32(H) / np.float32(2)))
+    ix = np.where(valid, x2, 0).astype(np.int32)
+    iy = np.where(valid, y2, 0).astype(np.int32)
+    return valid, ix, iy
+
+
+def make_bands(bw_, bh_):
+    """make_bands<16, true, 3072> for an unclipped box of bw_ x bh_ pixels: (nbx, nby, bw, bh, sy)"""
+    bw = min(bw_, PITCH)
+    pitch = max((bw + 15) & ~15, 16)
+    rows = CAP // pitch
+    bh = min(bh_, rows)
+    sy = rows - 3
+    nbx = (bw_ - bw + STEP_X - 1) // STEP_X + 1 if bw_ > bw else 1
+    nby = (bh_ - bh + sy - 1) // sy + 1 if bh_ > bh else 1
+    return nbx, nby, bw, bh, sy
+
+
+def census(flow):
+    """Counts over every 64 x 16 tile of flow [B, 2, H, W] (W % 4 == 0: the tiled kernels' precondition)."""
+    B, _, H, W = flow.shape
+    assert W % 4 == 0 and W >= 8
+    valid, ix, iy = locate(flow)
+    c0, c1 = np.maximum(ix - 1, 0), np.minimum(ix + 2, W - 1)      # the clamped 4 x 4 window of a site
+    r0, r1 = np.maximum(iy - 1, 0), np.minimum(iy + 2, H - 1)
+    out = dict(tiles=0, empty=0, nbx_gt1=0, nby_gt1=0, capped=0, max_bands_run=0, slow=0, split_lanes=0, mixed_lanes=0,
+               valid=int(valid.sum()), sites=int(valid.size), ragged_rows=H % TH, ragged_cols=W % TW)
+    for b in range(B):
+        for ty in range((H + TH - 1) // TH):
+            for tx in range((W + TW - 1) // TW):
+                ys, xs = slice(ty * TH, min(ty * TH + TH, H)), slice(tx * TW, min(tx * TW + TW, W))
+                v = valid[b, ys, xs]
+                out["tiles"] += 1
+                nv = v.reshape(v.shape[0], -1, 4).sum(-1)
+                out["mixed_lanes"] += int(((nv > 0) & (nv < 4)).sum())
+                if not v.any():                                    # box.w == 0: one round that copies the input pixels
+                    out["empty"] += 1
+                    continue
+                C0, C1, R0, R1 = c0[b, ys, xs], c1[b, ys, xs], r0[b, ys, xs], r1[b, ys, xs]
+                # tile_bbox
+                bx0 = int(C0[v].min()) & ~3
+                bw_ = (int(C1[v].max()) | 3) + 1 - bx0
+                by0 = int(R0[v].min())
+                bh_ = int(R1[v].max()) + 1 - by0
+                nbx, nby, bw, bh, sy = make_bands(bw_, bh_)
+                n = min(nbx * nby, MAX_BANDS)
+                out["nbx_gt1"] += nbx > 1
+                out["nby_gt1"] += nby > 1
+                out["capped"] += nbx * nby > MAX_BANDS
+                done = np.zeros_like(v)
+                run = 0
+                for bi in range(n):
+                    # band_region, fi_covered
+                    rx0 = min(bx0 + (bi % nbx) * STEP_X, bx0 + bw_ - bw)
+                    ry0 = min(by0 + (bi // nbx) * sy, by0 + bh_ - bh)
+                    sel = v & (C0 >= rx0) & (C1 < rx0 + bw) & (R0 >= ry0) & (R1 < ry0 + bh) & ~done
+                    if bi > 0 and not sel.any():                   # the vote: nobody needs this band
+                        continue
+                    run += 1
+                    done |= sel
+                    wr = sel | ~v if bi == 0 else sel              # band 0 also writes the out-of-range sites
+                    w4 = wr.reshape(wr.shape[0], -1, 4).sum(-1)
+                    out["split_lanes"] += int(((w4 > 0) & (w4 < 4)).sum())
+                out["max_bands_run"] = max(out["max_bands_run"], run)
+                out["slow"] += int((v & ~done).sum())
+    return {k: int(x) for k, x in out.items()}
