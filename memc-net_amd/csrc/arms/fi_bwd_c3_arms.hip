@@ -58,12 +58,7 @@ __device__ __forceinline__ void fi_bwd_phase1(const Region &r, unsigned fast, Fi
                                               float *gin2_b, int64_t s2c, unsigned o2, float *gin3_b, int64_t s3c,
                                               unsigned o3)
 {
-    // keep tap splats / weights inside the caller's band loop (hoisted, they spill)
-#pragma unroll
-    for (int k = 0; k < 16; k++)
-        asm volatile("" : "+v"(tp[k][0]), "+v"(tp[k][1]), "+v"(tp[k][2]), "+v"(tp[k][3]));
-#pragma unroll
-    for (int j = 0; j < 4; j++) asm volatile("" : "+v"(g.ix[j]), "+v"(g.iy[j]), "+v"(g.a[j]), "+v"(g.b[j]));
+    MEMC_FI_LAUNDER(tp, g);                    // inside the caller's band loop
     // Only quads that this band owns completely (the common case) take this path -- ONE exec-masked region
     // without inner control flow, every store unconditional (the buffers are zero-filled by the caller:
     // 0 + g == g); mixed quads are redone per site by fi_bwd_site_taps.  Any load or data-dependent merge inside
@@ -179,19 +174,7 @@ __global__ __launch_bounds__(256, MINW) void fi_bwd_tiled_c3(
     if (TR) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     trace_mark<TR>(1);                                         // inputs have arrived
 
-    FiSite4 g;
-    g.valid = 0;
-    int cmin = INT_MAX, cmax = -1, rmin = INT_MAX, rmax = -1;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const FiSite s = fi_locate(x + j, y, W, H, fx4[j], fy4[j]);
-        g.ix[j] = s.ix; g.iy[j] = s.iy; g.a[j] = s.a; g.b[j] = s.b;
-        if (inb && s.valid) {
-            g.valid |= 1u << j;
-            cmin = min(cmin, max(s.ix - 1, 0));  cmax = max(cmax, min(s.ix + 2, W - 1));
-            rmin = min(rmin, max(s.iy - 1, 0));  rmax = max(rmax, min(s.iy + 2, H - 1));
-        }
-    }
+    MEMC_FI_SITES(g, x, y, W, H, inb, fx4, fy4);
     const BBox box = tile_bbox<LX>(cmin, cmax, rmin, rmax, bb);
     const Bands bands = make_bands<LX, false>(box);
     const float *in_b = in1 + b * s1b;

@@ -26,15 +26,8 @@ __global__ __launch_bounds__(512) void fi_fwd_refshape(
     float *out_p = out + b * s1b + (int64_t)y * s1h + x;
     if (s.valid) {
         const int L = s.ix + 1 - fs / 2, T = s.iy + 1 - fs / 2, R = L + fs, Bm = T + fs;
-        for (int c = 0; c < C; c++) {
-            const float *p = in_b + c * s1c;
-            const float TL = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, L, s.ix);
-            const float TR = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, s.ix + 1, R - 1);
-            const float BL = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, L, s.ix);
-            const float BR = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, s.ix + 1, R - 1);
-            out_p[c * s1c] = (1 - s.a) * (1 - s.b) * TL + s.a * (1 - s.b) * TR +
-                             (1 - s.a) * s.b * BL + s.a * s.b * BR;
-        }
+        for (int c = 0; c < C; c++)
+            out_p[c * s1c] = fi_site_chan(s, fs, L, T, R, Bm, W, H, in_b + c * s1c, s1h, tap_p, s3c);
     } else {
         const float *p = in_b + (int64_t)y * s1h + x;
         for (int c = 0; c < C; c++) out_p[c * s1c] = p[c * s1c];

@@ -56,19 +56,7 @@
     if (TR) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     trace_mark<TR>(1);                                         // inputs have arrived
 
-    FiSite4 g;
-    g.valid = 0;
-    int cmin = INT_MAX, cmax = -1, rmin = INT_MAX, rmax = -1;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const FiSite s = fi_locate(x + j, y, W, H, fx4[j], fy4[j]);
-        g.ix[j] = s.ix; g.iy[j] = s.iy; g.a[j] = s.a; g.b[j] = s.b;
-        if (inb && s.valid) {
-            g.valid |= 1u << j;
-            cmin = min(cmin, max(s.ix - 1, 0));  cmax = max(cmax, min(s.ix + 2, W - 1));
-            rmin = min(rmin, max(s.iy - 1, 0));  rmax = max(rmax, min(s.iy + 2, H - 1));
-        }
-    }
+    MEMC_FI_SITES(g, x, y, W, H, inb, fx4, fy4);
     // per-site bounds of the packed planes (memc_pk.hpp): s = (the site's largest |gradoutput|) x (its largest |tap|),
     // published per wave and handed over by the barrier inside tile_bbox
     int sbits[4] = {0, 0, 0, 0}, gbits[4] = {0, 0, 0, 0}, tmax = 0;

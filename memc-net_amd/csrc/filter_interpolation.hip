@@ -14,6 +14,11 @@
 //     4x4 windows overlap between neighbouring lanes and rows;
 //   * the workgroup->tile map is XCD-chunked (memc_common.hpp) so halo rows are shared inside one L2;
 //   * 64-bit batch/channel offsets (4K x batch 8 x 64 channels exceeds 2^31 elements), 32-bit in-plane.
+//
+// The per-site pieces -- the geometry of a lane's four sites (MEMC_FI_SITES), the laundering that keeps loop-invariant
+// arithmetic inside the band and chunk loops (MEMC_FI_LAUNDER), the LDS gather (fi_gather), one site from global memory
+// (fi_quad_sum, fi_site_chan, the body of fi_site_scalar) -- are memc_fi.hpp's, shared with the backward kernels and
+// with the half-precision library (lp_filter_interpolation.hip).
 #include "memc_common.hpp"
 #include "memc_internal.h"
 #include "memc_tile.hpp"
@@ -34,74 +39,18 @@ namespace memc {
 //   4. one dwordx4 store per channel (non-temporal).
 //   C > 4 loops steps 2-4 over chunks of four channels with the taps and site geometry kept in registers.
 // --------------------------------------------------------------------------------------------------
-// Scalar evaluation of ONE site for channels [0, nch) of `plane0`, everything read from global memory
-// (flow, taps, image): the rare path for sites whose source window is not in the staged LDS region, and the
-// body of the any-filter-size kernel.  Same arithmetic order as the fast path.
-
+// ONE site from global memory, all channels: the sites that no staged band covers (the body: memc_fi.hpp).
 __device__ __noinline__ void fi_site_scalar(int x, int y, int W, int H, int nch, int fs,
                                             const float *plane0, int64_t s1c, int s1h,
                                             const float *flow_p, int64_t s2c, const float *tap_p, int64_t s3c,
                                             float *out_p)
-{
-    const float fx = flow_p[0], fy = flow_p[s2c];
-    const FiSite s = fi_locate(x, y, W, H, fx, fy);
-    if (s.valid) {
-        const int L = s.ix + 1 - fs / 2, T = s.iy + 1 - fs / 2, R = L + fs, Bm = T + fs;
-        for (int c = 0; c < nch; c++) {
-            const float *p = plane0 + c * s1c;
-            const float TL = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, L, s.ix);
-            const float TR = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, s.ix + 1, R - 1);
-            const float BL = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, L, s.ix);
-            const float BR = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, s.ix + 1, R - 1);
-            out_p[c * s1c] = (1 - s.a) * (1 - s.b) * TL + s.a * (1 - s.b) * TR +
-                             (1 - s.a) * s.b * BL + s.a * s.b * BR;
-        }
-    } else {
-        const float *p = plane0 + (int64_t)y * s1h + x;
-        for (int c = 0; c < nch; c++) out_p[c * s1c] = p[c * s1c];
-    }
-}
+MEMC_FI_SITE_SCALAR_BODY(F32, F32, int)
+#undef MEMC_FI_SITE_SCALAR_BODY
 
 // one chunk of NCH (1..4) channels: stage -> gather -> store.  Everything indexed by channel or site is
 // compile-time unrolled (run-time indexed vectors would live in scratch) and the hot path is branch-free:
 // a site whose window is not staged still issues its 16 LDS reads (at pixel 0, harmless) and is redone
 // afterwards by fi_site_scalar (at the end of the kernel, once for all channels).
-// Gather + blend of the sites selected by `sel` (bit j) from the staged band; other sites keep their `res`.
-// Branch-free: unselected sites still issue their 16 LDS reads (at pixel 0, harmless).
-template <int LX, int NCH>
-__device__ __forceinline__ void fi_gather(const Region &r, const FiSite4 &g, const f32x4 (&tp)[16], unsigned sel,
-                                          int W, int H, const f32x4 *tile, f32x4 (&res)[4])
-{
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const bool on = (sel >> j) & 1;
-        int ro[4], co[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            ro[k] = on ? (clampi(g.iy[j] - 1 + k, H - 1) - r.y0) * r.pitch : 0;
-            co[k] = on ? swz_col(clampi(g.ix[j] - 1 + k, W - 1) - r.x0) : 0;
-        }
-        // quadrant sums, row-major inside each quadrant as in the reference (rows 0,1 top; 2,3 bottom)
-        f32x4 TL = {0.f, 0.f, 0.f, 0.f}, TR = TL, BL = TL, BR = TL;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            f32x4 v[4];
-#pragma unroll
-            for (int m = 0; m < 4; m++) v[m] = tile[ro[k] + co[m]];
-            if (k < 2) {
-                TL += v[0] * tp[k * 4 + 0][j];  TL += v[1] * tp[k * 4 + 1][j];
-                TR += v[2] * tp[k * 4 + 2][j];  TR += v[3] * tp[k * 4 + 3][j];
-            } else {
-                BL += v[0] * tp[k * 4 + 0][j];  BL += v[1] * tp[k * 4 + 1][j];
-                BR += v[2] * tp[k * 4 + 2][j];  BR += v[3] * tp[k * 4 + 3][j];
-            }
-        }
-        const float a = g.a[j], bt = g.b[j];
-        const f32x4 val = ((1 - a) * (1 - bt)) * TL + (a * (1 - bt)) * TR + ((1 - a) * bt) * BL + (a * bt) * BR;
-        res[j] = on ? val : res[j];
-    }
-}
-
 template <int LX, int NCH>
 __device__ __forceinline__ void fi_gather_store(
     const Region &r, const FiSite4 &g, const f32x4 (&tp)[16], bool inb, int x, int y, int W, int H,
@@ -215,19 +164,7 @@ __global__ __launch_bounds__(NT, (NT == 256 && !RAGW) ? 2 : 1) void fi_fwd_tiled
 #pragma unroll
     for (int k = 0; k < 16; k++) tp[k] = ld_stream4(tap_p + k * s3c);
 
-    FiSite4 g;
-    g.valid = 0;
-    int cmin = INT_MAX, cmax = -1, rmin = INT_MAX, rmax = -1;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const FiSite s = fi_locate(x + j, y, W, H, fx4[j], fy4[j]);
-        g.ix[j] = s.ix; g.iy[j] = s.iy; g.a[j] = s.a; g.b[j] = s.b;
-        if (inb && s.valid) {
-            g.valid |= 1u << j;
-            cmin = min(cmin, max(s.ix - 1, 0));  cmax = max(cmax, min(s.ix + 2, W - 1));
-            rmin = min(rmin, max(s.iy - 1, 0));  rmax = max(rmax, min(s.iy + 2, H - 1));
-        }
-    }
+    MEMC_FI_SITES(g, x, y, W, H, inb, fx4, fy4);
     const BBox box = tile_bbox<LX, NT>(cmin, cmax, rmin, rmax, bb);
     const Bands bands = make_bands<LX, true, CAP>(box);
     const float *in_b = in1 + b * s1b;
@@ -267,12 +204,7 @@ __global__ __launch_bounds__(NT, (NT == 256 && !RAGW) ? 2 : 1) void fi_fwd_tiled
             // chunk -- harmless, keeps the loads unconditional)
             const int cn = c0 + 4 < C ? c0 + 4 : c0;
             if (ABL != 2) stage_load(cn);
-            // keep the loop-invariant tap splats / LDS addresses inside the loop (see fi_fwd_tiled_fs4)
-#pragma unroll
-            for (int k = 0; k < 16; k++)
-                asm volatile("" : "+v"(tp[k][0]), "+v"(tp[k][1]), "+v"(tp[k][2]), "+v"(tp[k][3]));
-#pragma unroll
-            for (int j = 0; j < 4; j++) asm volatile("" : "+v"(g.ix[j]), "+v"(g.iy[j]), "+v"(g.a[j]), "+v"(g.b[j]));
+            MEMC_FI_LAUNDER(tp, g);
             f32x4 res[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) res[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -394,19 +326,7 @@ __global__ __launch_bounds__(256, MINW) void fi_fwd_tiled_fs4(
     for (int k = 0; k < 16; k++) tp[k] = ld_stream4(tap_p + k * s3c);
 
     // 2. site geometry and this lane's source box
-    FiSite4 g;
-    g.valid = 0;
-    int cmin = INT_MAX, cmax = -1, rmin = INT_MAX, rmax = -1;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const FiSite s = fi_locate(x + j, y, W, H, fx4[j], fy4[j]);
-        g.ix[j] = s.ix; g.iy[j] = s.iy; g.a[j] = s.a; g.b[j] = s.b;
-        if (inb && s.valid) {
-            g.valid |= 1u << j;
-            cmin = min(cmin, max(s.ix - 1, 0));  cmax = max(cmax, min(s.ix + 2, W - 1));
-            rmin = min(rmin, max(s.iy - 1, 0));  rmax = max(rmax, min(s.iy + 2, H - 1));
-        }
-    }
+    MEMC_FI_SITES(g, x, y, W, H, inb, fx4, fy4);
     // 3. source box, swept in bands when it does not fit the LDS budget (memc_tile.hpp)
     const BBox box = tile_bbox<LX>(cmin, cmax, rmin, rmax, bb);
     const Bands bands = make_bands<LX, true, CAP>(box);
@@ -430,12 +350,7 @@ __global__ __launch_bounds__(256, MINW) void fi_fwd_tiled_fs4(
             done |= sel;
             tile_stage<LX, 3, 256, RAGW, ITS>(rb, in_b, s1c, s1h, tile);
             __syncthreads();
-            // keep tap splats / blend weights inside the loop (hoisted, they spill: see the chunk loop below)
-#pragma unroll
-            for (int k = 0; k < 16; k++)
-                asm volatile("" : "+v"(tp[k][0]), "+v"(tp[k][1]), "+v"(tp[k][2]), "+v"(tp[k][3]));
-#pragma unroll
-            for (int j = 0; j < 4; j++) asm volatile("" : "+v"(g.ix[j]), "+v"(g.iy[j]), "+v"(g.a[j]), "+v"(g.b[j]));
+            MEMC_FI_LAUNDER(tp, g);
             fi_gather<LX, 3>(rb, g, tp, sel, W, H, tile, res);
         }
         slow = inb ? g.valid & ~done : 0u;
@@ -466,15 +381,7 @@ __global__ __launch_bounds__(256, MINW) void fi_fwd_tiled_fs4(
 #pragma unroll 1
         for (; c0 + 4 <= C; c0 += 4) {
             if (c0 > 0) __syncthreads();                   // the previous chunk's gathers are done
-            // Everything the chunk body derives from the taps and the site geometry (tap splats for the
-            // packed FMAs, 64 LDS addresses, blend weights) is loop-invariant; hoisted out of the loop it
-            // needs ~400 more registers than exist and lands in scratch (1.5 KB per lane).  Laundering the
-            // inputs through empty asm statements once per iteration keeps that arithmetic in the loop.
-#pragma unroll
-            for (int k = 0; k < 16; k++)
-                asm volatile("" : "+v"(tp[k][0]), "+v"(tp[k][1]), "+v"(tp[k][2]), "+v"(tp[k][3]));
-#pragma unroll
-            for (int j = 0; j < 4; j++) asm volatile("" : "+v"(g.ix[j]), "+v"(g.iy[j]), "+v"(g.a[j]), "+v"(g.b[j]));
+            MEMC_FI_LAUNDER(tp, g);                        // (memc_fi.hpp: hoisted, the chunk body spills)
             fi_fwd_chunk<LX, 4, RAGW>(r, g, tp, inb, x, y, W, H, in_b + c0 * s1c, out_p + c0 * s1c, s1c, s1h, tile);
         }
         if (c0 < C) {                                      // tail of 1..3 channels
@@ -482,11 +389,7 @@ __global__ __launch_bounds__(256, MINW) void fi_fwd_tiled_fs4(
             const int nch = C - c0;
             const float *plane0 = in_b + c0 * s1c;
             float *o = out_p + c0 * s1c;
-#pragma unroll
-            for (int k = 0; k < 16; k++)                   // as above: keep the tail's arithmetic in the tail
-                asm volatile("" : "+v"(tp[k][0]), "+v"(tp[k][1]), "+v"(tp[k][2]), "+v"(tp[k][3]));
-#pragma unroll
-            for (int j = 0; j < 4; j++) asm volatile("" : "+v"(g.ix[j]), "+v"(g.iy[j]), "+v"(g.a[j]), "+v"(g.b[j]));
+            MEMC_FI_LAUNDER(tp, g);                        // as above: keep the tail's arithmetic in the tail
             if (nch == 3)      fi_fwd_chunk<LX, 3, RAGW>(r, g, tp, inb, x, y, W, H, plane0, o, s1c, s1h, tile);
             else if (nch == 2) fi_fwd_chunk<LX, 2, RAGW>(r, g, tp, inb, x, y, W, H, plane0, o, s1c, s1h, tile);
             else               fi_fwd_chunk<LX, 1, RAGW>(r, g, tp, inb, x, y, W, H, plane0, o, s1c, s1h, tile);
@@ -514,6 +417,7 @@ __device__ __forceinline__ f32x4 fi_site_vals3(int x, int y, int W, int H, const
     const FiSite s = fi_locate(x, y, W, H, fx, fy);
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (!s.valid) return v;                                // (callers only pass valid sites)
+    // (spelled out: through fi_site_chan of memc_fi.hpp this kernel compiles to other machine code)
     const int L = s.ix - 1, T = s.iy - 1, R = L + 4, Bm = T + 4;
 #pragma unroll 1
     for (int c = 0; c < 3; c++) {
@@ -565,19 +469,7 @@ __global__ __launch_bounds__(256, 2) void fi_fwd_blend_c3(
     // one direction: box -> (bands of) stage -> gather; returns the warped RGB of the lane's four sites
     auto warp = [&](const float *in_b, const float *flow_b, const float *filt_b, const f32x4 &fx4, const f32x4 &fy4,
                     f32x4 (&tp)[16], f32x4 (&res)[4]) {
-        FiSite4 g;
-        g.valid = 0;
-        int cmin = INT_MAX, cmax = -1, rmin = INT_MAX, rmax = -1;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const FiSite s = fi_locate(x + j, y, W, H, fx4[j], fy4[j]);
-            g.ix[j] = s.ix; g.iy[j] = s.iy; g.a[j] = s.a; g.b[j] = s.b;
-            if (inb && s.valid) {
-                g.valid |= 1u << j;
-                cmin = min(cmin, max(s.ix - 1, 0));  cmax = max(cmax, min(s.ix + 2, W - 1));
-                rmin = min(rmin, max(s.iy - 1, 0));  rmax = max(rmax, min(s.iy + 2, H - 1));
-            }
-        }
+        MEMC_FI_SITES(g, x, y, W, H, inb, fx4, fy4);
         const BBox box = tile_bbox<LX>(cmin, cmax, rmin, rmax, bb);
         const Bands bands = make_bands<LX>(box);
 #pragma unroll
@@ -591,12 +483,7 @@ __global__ __launch_bounds__(256, 2) void fi_fwd_blend_c3(
             done |= sel;
             tile_stage<LX, 3>(rb, in_b, s1c, s1h, tile);
             __syncthreads();
-            // keep tap splats / blend weights inside the loop (hoisted, they spill)
-#pragma unroll
-            for (int k = 0; k < 16; k++)
-                asm volatile("" : "+v"(tp[k][0]), "+v"(tp[k][1]), "+v"(tp[k][2]), "+v"(tp[k][3]));
-#pragma unroll
-            for (int j = 0; j < 4; j++) asm volatile("" : "+v"(g.ix[j]), "+v"(g.iy[j]), "+v"(g.a[j]), "+v"(g.b[j]));
+            MEMC_FI_LAUNDER(tp, g);
             fi_gather<LX, 3>(rb, g, tp, sel, W, H, tile, res);
         }
         if (!inb) return;
@@ -679,19 +566,7 @@ __global__ __launch_bounds__(256, 2) void fi_fwd_ctx_img(
 #pragma unroll
     for (int k = 0; k < 16; k++) tp[k] = ld_stream4(tap_p + k * s3c);
 
-    FiSite4 g;
-    g.valid = 0;
-    int cmin = INT_MAX, cmax = -1, rmin = INT_MAX, rmax = -1;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const FiSite s = fi_locate(x + j, y, W, H, fx4[j], fy4[j]);
-        g.ix[j] = s.ix; g.iy[j] = s.iy; g.a[j] = s.a; g.b[j] = s.b;
-        if (inb && s.valid) {
-            g.valid |= 1u << j;
-            cmin = min(cmin, max(s.ix - 1, 0));  cmax = max(cmax, min(s.ix + 2, W - 1));
-            rmin = min(rmin, max(s.iy - 1, 0));  rmax = max(rmax, min(s.iy + 2, H - 1));
-        }
-    }
+    MEMC_FI_SITES(g, x, y, W, H, inb, fx4, fy4);
     const BBox box = tile_bbox<LX>(cmin, cmax, rmin, rmax, bb);
     const Bands bands = make_bands<LX>(box);
     const float *img_b = img + b * sib;
@@ -736,12 +611,7 @@ __global__ __launch_bounds__(256, 2) void fi_fwd_ctx_img(
             // chunk -- harmless, keeps the loads unconditional)
             const int cn = vc + 1 < nchunks ? vc * 4 : (vc - 1) * 4;      // context channel of the next chunk
             tile_stage_load<4>(r, sl, in_b + cn * s1c, s1c, s1h, sr);
-            // keep the loop-invariant tap splats / LDS addresses inside the loop (see fi_fwd_tiled_fs4)
-#pragma unroll
-            for (int k = 0; k < 16; k++)
-                asm volatile("" : "+v"(tp[k][0]), "+v"(tp[k][1]), "+v"(tp[k][2]), "+v"(tp[k][3]));
-#pragma unroll
-            for (int j = 0; j < 4; j++) asm volatile("" : "+v"(g.ix[j]), "+v"(g.iy[j]), "+v"(g.a[j]), "+v"(g.b[j]));
+            MEMC_FI_LAUNDER(tp, g);
             f32x4 res[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) res[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -929,15 +799,8 @@ __global__ __launch_bounds__(256) void fi_fwd_generic(
     float *out_p = out + b * s1b + (int64_t)y * s1h + x;
     if (s.valid) {
         const int L = s.ix + 1 - fs / 2, T = s.iy + 1 - fs / 2, R = L + fs, Bm = T + fs;
-        for (int c = 0; c < C; c++) {
-            const float *p = in_b + c * s1c;
-            const float TL = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, L, s.ix);
-            const float TR = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, s.ix + 1, R - 1);
-            const float BL = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, L, s.ix);
-            const float BR = fi_quad_sum(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, s.ix + 1, R - 1);
-            out_p[c * s1c] = (1 - s.a) * (1 - s.b) * TL + s.a * (1 - s.b) * TR +
-                             (1 - s.a) * s.b * BL + s.a * s.b * BR;
-        }
+        for (int c = 0; c < C; c++)
+            out_p[c * s1c] = fi_site_chan(s, fs, L, T, R, Bm, W, H, in_b + c * s1c, s1h, tap_p, s3c);
     } else {
         const float *p = in_b + (int64_t)y * s1h + x;
         for (int c = 0; c < C; c++) out_p[c * s1c] = p[c * s1c];

@@ -3,61 +3,22 @@
 // Replaces my_package/src/my_lib_cuda.c:364-983 of the reference: read sizes/strides from the tensor
 // descriptors, validate, call the kernel launcher on the caller's stream, return 0 / -1.
 //
-// Checks: every check the reference performs (cited per function) is performed here.  In addition the
-// descriptors that the kernels index with ANOTHER tensor's strides (output / gradoutput / gradinput1 with
-// input1's, gradinput2 with input2's, gradinput3 with input3's, exactly as my_lib_kernel.cu does) must
-// really have those b/c/h strides, all w-strides must be 1 and all strides must fit the launcher ABI's
-// `int`; the reference leaves those cases unchecked and silently reads/writes the wrong cells.
+// Checks: every check the reference performs (cited per function) is performed here, and those the kernels rely on
+// beyond them; the checks themselves are memc_desc.hpp's, shared with the half-precision libraries.
 #include "memc_internal.h"
+#include "memc_desc.hpp"
 
 #include <math.h>
 #include <stdint.h>
 
 namespace {
 
+using namespace memc;            // the descriptor checks: memc_desc.hpp
 constexpr int kErr = -1;
-
-inline bool fits_int(const memc_tensor4 *t)
-{
-    for (int i = 0; i < 4; i++)
-        if (t->size[i] < 0 || t->size[i] > INT32_MAX || t->stride[i] < 0 || t->stride[i] > INT32_MAX)
-            return false;
-    return true;
-}
-
-inline bool same_shape(const memc_tensor4 *a, const memc_tensor4 *b)
-{
-    return a->size[0] == b->size[0] && a->size[1] == b->size[1] && a->size[2] == b->size[2] &&
-           a->size[3] == b->size[3];
-}
-
-// same b/c/h strides (the kernels index `b` with `a`'s strides) and unit w stride
-inline bool same_layout(const memc_tensor4 *a, const memc_tensor4 *b)
-{
-    if (!same_shape(a, b)) return false;
-    for (int i = 0; i < 3; i++)                 // the stride of a size-1 dimension is never used
-        if (a->size[i] > 1 && a->stride[i] != b->stride[i]) return false;
-    return true;
-}
-
-inline int64_t numel(const memc_tensor4 *t) { return t->size[0] * t->size[1] * t->size[2] * t->size[3]; }
-
-// usable descriptor: sizes/strides fit the launcher ABI, unit w stride, non-null data unless empty
-inline bool ok(const memc_tensor4 *t)
-{
-    return t && fits_int(t) && (t->stride[3] == 1 || t->size[3] <= 1) && (t->data || numel(t) == 0);
-}
 
 inline int nelem(const memc_tensor4 *t) { return (int)numel(t); }   // ignored by the launchers
 
 #define S4(t) (int)(t)->stride[0], (int)(t)->stride[1], (int)(t)->stride[2], (int)(t)->stride[3]
-
-// flow tensor [N,2,H,W] matching input1 [N,C,H,W]; my_lib_cuda.c:375-381
-inline bool flow_matches(const memc_tensor4 *in1, const memc_tensor4 *flow)
-{
-    return flow->size[0] == in1->size[0] && flow->size[1] == 2 && flow->size[2] == in1->size[2] &&
-           flow->size[3] == in1->size[3];
-}
 
 int bilinear_forward(bool require_c3, memc_stream_t stream, const memc_tensor4 *input1,
                      const memc_tensor4 *input2, const memc_tensor4 *output)
@@ -134,9 +95,7 @@ int FilterInterpolationLayer_gpu_forward(memc_stream_t stream, const memc_tensor
 {
     if (!ok(input1) || !ok(input2) || !ok(input3) || !ok(output)) return kErr;    // my_lib_cuda.c:641-643
     if (!flow_matches(input1, input2)) return kErr;                                 // :611-617
-    if (input3->size[0] != input1->size[0] || input3->size[2] != input1->size[2] ||
-        input3->size[3] != input1->size[3])
-        return kErr;
+    if (!taps_match(input1, input3)) return kErr;
     const int filter_size = (int)sqrt((float)input3->size[1]);                      // :619-620
     if (filter_size < 1) return kErr;
     if (!same_layout(input1, output)) return kErr;                                  // :644-645 (+h)
@@ -156,9 +115,7 @@ int FilterInterpolationLayer_gpu_backward(memc_stream_t stream, const memc_tenso
         !ok(gradinput2) || !ok(gradinput3))
         return kErr;                                                                // :716-718
     if (!flow_matches(input1, input2)) return kErr;                                 // :685-691
-    if (input3->size[0] != input1->size[0] || input3->size[2] != input1->size[2] ||
-        input3->size[3] != input1->size[3])
-        return kErr;
+    if (!taps_match(input1, input3)) return kErr;
     const int filter_size = (int)sqrt((float)input3->size[1]);                      // :693-694
     if (filter_size < 1) return kErr;
     if ((gradinput1 && !same_layout(input1, gradinput1)) || !same_layout(input2, gradinput2) ||
@@ -186,9 +143,7 @@ int FilterInterpolationBlendLayer_gpu_forward(memc_stream_t stream, const memc_t
     if (!same_layout(input0, input2) || !same_layout(input0, output) || !same_layout(flow0, flow1) ||
         !same_layout(filter0, filter1) || !same_layout(occlusion0, occlusion1))
         return kErr;
-    if (filter0->size[0] != input0->size[0] || filter0->size[2] != input0->size[2] ||
-        filter0->size[3] != input0->size[3])
-        return kErr;
+    if (!taps_match(input0, filter0)) return kErr;
     if (occlusion0->size[0] != input0->size[0] || occlusion0->size[1] != 1 ||
         occlusion0->size[2] != input0->size[2] || occlusion0->size[3] != input0->size[3])
         return kErr;
@@ -216,8 +171,7 @@ int FilterInterpolationCtxLayer_gpu_forward(memc_stream_t stream, const memc_ten
     if (blend && (!ok(prev) || !ok(occlusion_prev) || !ok(occlusion_this))) return kErr;
     if (image->size[1] != 3 || !flow_matches(image, flow) || !flow_matches(context, flow)) return kErr;
     if (!same_layout(image, image_out) || !same_layout(context, context_out)) return kErr;
-    if (filter->size[0] != image->size[0] || filter->size[2] != image->size[2] || filter->size[3] != image->size[3])
-        return kErr;
+    if (!taps_match(image, filter)) return kErr;
     if (blend) {
         if (!same_layout(image, prev) || !same_layout(occlusion_prev, occlusion_this)) return kErr;
         if (occlusion_prev->size[0] != image->size[0] || occlusion_prev->size[1] != 1 ||

@@ -11,6 +11,7 @@
 // sum gradinput2 of sites that no LDS band covers in different orders (fi_bwd_site_scalar vs fi_bwd_site_taps).
 #include "memc_common.hpp"
 #include "memc_fi_bwd_c3.hpp"
+#include "memc_desc.hpp"
 #include "memc_warp_lp_grad.h"
 
 #include <math.h>
@@ -45,44 +46,6 @@ namespace {
 using namespace memc;
 constexpr int kErr = -1;
 constexpr int kNotCovered = 1;
-
-bool fits_int(const memc_tensor4 *t)
-{
-    for (int i = 0; i < 4; i++)
-        if (t->size[i] < 0 || t->size[i] > INT32_MAX || t->stride[i] < 0 || t->stride[i] > INT32_MAX) return false;
-    return true;
-}
-int64_t numel(const memc_tensor4 *t) { return t->size[0] * t->size[1] * t->size[2] * t->size[3]; }
-// usable descriptor: sizes / strides fit int32, unit w stride, non-null data unless empty (layer_api.cpp)
-bool ok(const memc_tensor4 *t) { return t && fits_int(t) && (t->stride[3] == 1 || t->size[3] <= 1) && (t->data || numel(t) == 0); }
-bool same_shape(const memc_tensor4 *a, const memc_tensor4 *b)
-{
-    return a->size[0] == b->size[0] && a->size[1] == b->size[1] && a->size[2] == b->size[2] && a->size[3] == b->size[3];
-}
-// same b/c/h strides (the kernel indexes `b` with `a`'s strides); the stride of a size-1 dimension is never used
-bool same_layout(const memc_tensor4 *a, const memc_tensor4 *b)
-{
-    if (!same_shape(a, b)) return false;
-    for (int i = 0; i < 3; i++)
-        if (a->size[i] > 1 && a->stride[i] != b->stride[i]) return false;
-    return true;
-}
-// flow [N, 2, H, W] and taps [N, K, H, W] matching input1 [N, C, H, W] (my_lib_cuda.c:685-694)
-bool flow_matches(const memc_tensor4 *in1, const memc_tensor4 *flow)
-{
-    return flow->size[0] == in1->size[0] && flow->size[1] == 2 && flow->size[2] == in1->size[2] && flow->size[3] == in1->size[3];
-}
-bool taps_match(const memc_tensor4 *in1, const memc_tensor4 *filt)
-{
-    return filt->size[0] == in1->size[0] && filt->size[2] == in1->size[2] && filt->size[3] == in1->size[3];
-}
-// T quads of the tiled kernel: strides of every walked dimension a multiple of four elements, 8-byte aligned base
-bool quad_ok(const memc_tensor4 *t)
-{
-    for (int i = 0; i < 3; i++)
-        if (t->size[i] > 1 && t->stride[i] % 4 != 0) return false;
-    return reinterpret_cast<uintptr_t>(t->data) % 8 == 0;
-}
 
 inline int64_t S(const memc_tensor4 *t, int i) { return t->stride[i]; }
 
@@ -143,8 +106,7 @@ int FilterInterpolationLayer_gpu_backward_lp(memc_stream_t stream, memc_dtype pa
                                              const memc_tensor4 *gradinput1, const memc_tensor4 *gradinput2,
                                              const memc_tensor4 *gradinput3)
 {
-    if (payload != MEMC_F16 && payload != MEMC_BF16) return kErr;
-    if ((flowt != MEMC_F32 && flowt != payload) || (goutt != MEMC_F32 && goutt != payload)) return kErr;
+    if (!dtypes_ok(payload, flowt) || !dtypes_ok(payload, goutt)) return kErr;
     if (!ok(input1) || !ok(input2) || !ok(input3) || !ok(gradoutput) || (gradinput1 && !ok(gradinput1)) ||
         !ok(gradinput2) || !ok(gradinput3))
         return kErr;                                                                // my_lib_cuda.c:716-718

@@ -10,11 +10,13 @@
 //                                   flight while this one is gathered), a ragged last chunk re-reads the last plane;
 //   fi_blend_lp_tiled<T, FT>        fi_fwd_blend_c3: both directions' streams up front, one box -> stage -> gather round each;
 //   fi_fwd_lp_direct / fi_blend_lp_direct   one lane per site, any filter size, any width, any alignment.
-// The LDS holds fp32 pixel quads (staging widens), so the gather and its arithmetic are the fp32 kernels' verbatim.
+// The LDS holds fp32 pixel quads (staging widens), so the gather and its arithmetic are the fp32 kernels' own: the site
+// geometry, the gather and the one-site paths from global memory are memc_fi.hpp's, the descriptor checks memc_desc.hpp's.
 #include "memc_common.hpp"
 #include "memc_tile.hpp"
 #include "memc_fi.hpp"
 #include "memc_lp.hpp"
+#include "memc_desc.hpp"
 #include "memc_warp_lp.h"
 
 #include <math.h>
@@ -23,112 +25,16 @@ namespace memc {
 
 thread_local const char *t_lp_path = "";
 
-// fi_gather of filter_interpolation.hip: gather + blend of the sites selected by `sel` (bit j) from the staged band;
-// other sites keep their `res`.  Branch-free: unselected sites still issue their 16 LDS reads (at pixel 0, harmless).
-__device__ __forceinline__ void lp_gather(const Region &r, const FiSite4 &g, const f32x4 (&tp)[16], unsigned sel, int W,
-                                          int H, const f32x4 *tile, f32x4 (&res)[4])
+// MEMC_FI_SITES and MEMC_FI_LAUNDER (memc_fi.hpp) as functions, for fi_blend_lp_tiled alone: expanded in place, as in
+// every other kernel, its fp16 instantiation is 2 % slower (profiles/r08_refactor_lowp_ab.txt).
+__device__ __forceinline__ FiSite4 fi_sites_fn(int x, int y, int W, int H, bool inb, const f32x4 &fx4, const f32x4 &fy4,
+                                               int &cmin_, int &cmax_, int &rmin_, int &rmax_)
 {
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const bool on = (sel >> j) & 1;
-        int ro[4], co[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            ro[k] = on ? (clampi(g.iy[j] - 1 + k, H - 1) - r.y0) * r.pitch : 0;
-            co[k] = on ? swz_col(clampi(g.ix[j] - 1 + k, W - 1) - r.x0) : 0;
-        }
-        // quadrant sums, row-major inside each quadrant as in the reference (rows 0,1 top; 2,3 bottom)
-        f32x4 TL = {0.f, 0.f, 0.f, 0.f}, TR = TL, BL = TL, BR = TL;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            f32x4 v[4];
-#pragma unroll
-            for (int m = 0; m < 4; m++) v[m] = tile[ro[k] + co[m]];
-            if (k < 2) {
-                TL += v[0] * tp[k * 4 + 0][j];  TL += v[1] * tp[k * 4 + 1][j];
-                TR += v[2] * tp[k * 4 + 2][j];  TR += v[3] * tp[k * 4 + 3][j];
-            } else {
-                BL += v[0] * tp[k * 4 + 0][j];  BL += v[1] * tp[k * 4 + 1][j];
-                BR += v[2] * tp[k * 4 + 2][j];  BR += v[3] * tp[k * 4 + 3][j];
-            }
-        }
-        const float a = g.a[j], bt = g.b[j];
-        const f32x4 val = ((1 - a) * (1 - bt)) * TL + (a * (1 - bt)) * TR + ((1 - a) * bt) * BL + (a * bt) * BR;
-        res[j] = on ? val : res[j];
-    }
-}
-
-// One channel of one valid site from global memory, any filter size (fi_quad_sum / fi_site_scalar of the fp32 path).
-template <class T>
-__device__ __forceinline__ float lp_quad_sum(const st_t<T> *p, int s1h, int W, int H, const st_t<T> *tap_p, int64_t s3c,
-                                             int fs, int L, int Tp, int j0, int j1, int i0, int i1)
-{
-    float acc = 0.0f;
-    for (int j = j0; j <= j1; j++) {
-        const int64_t jj = (int64_t)clampi(j, H - 1) * s1h;
-        for (int i = i0; i <= i1; i++)
-            acc += widen<T>(p[jj + clampi(i, W - 1)]) * widen<T>(tap_p[((j - Tp) * fs + (i - L)) * s3c]);
-    }
-    return acc;
-}
-
-template <class T>
-__device__ __forceinline__ float lp_site_chan(const FiSite &s, int fs, int W, int H, const st_t<T> *p, int s1h,
-                                              const st_t<T> *tap_p, int64_t s3c)
-{
-    const int L = s.ix + 1 - fs / 2, Tp = s.iy + 1 - fs / 2, R = L + fs, Bm = Tp + fs;
-    const float TL = lp_quad_sum<T>(p, s1h, W, H, tap_p, s3c, fs, L, Tp, Tp, s.iy, L, s.ix);
-    const float TR = lp_quad_sum<T>(p, s1h, W, H, tap_p, s3c, fs, L, Tp, Tp, s.iy, s.ix + 1, R - 1);
-    const float BL = lp_quad_sum<T>(p, s1h, W, H, tap_p, s3c, fs, L, Tp, s.iy + 1, Bm - 1, L, s.ix);
-    const float BR = lp_quad_sum<T>(p, s1h, W, H, tap_p, s3c, fs, L, Tp, s.iy + 1, Bm - 1, s.ix + 1, R - 1);
-    return (1 - s.a) * (1 - s.b) * TL + s.a * (1 - s.b) * TR + (1 - s.a) * s.b * BL + s.a * s.b * BR;
-}
-
-// ONE site, all channels, everything from global memory: the sites no band covers, and the body of the direct kernel.
-template <class T, class FT>
-__device__ __noinline__ void lp_site_scalar(int x, int y, int W, int H, int nch, int fs, const st_t<T> *plane0, int64_t s1c,
-                                            int s1h, const st_t<FT> *flow_p, int64_t s2c, const st_t<T> *tap_p, int64_t s3c,
-                                            st_t<T> *out_p)
-{
-    const FiSite s = fi_locate(x, y, W, H, widen<FT>(flow_p[0]), widen<FT>(flow_p[s2c]));
-    if (s.valid) {
-        for (int c = 0; c < nch; c++)
-            out_p[c * s1c] = narrow<T>(lp_site_chan<T>(s, fs, W, H, plane0 + c * s1c, s1h, tap_p, s3c));
-    } else {
-        const st_t<T> *p = plane0 + (int64_t)y * s1h + x;
-        for (int c = 0; c < nch; c++) out_p[c * s1c] = p[c * s1c];     // out-of-range sites copy the input pixel
-    }
-}
-
-// site geometry of a lane's four sites and the box of their (clamped) windows
-__device__ __forceinline__ FiSite4 lp_sites(int x, int y, int W, int H, bool inb, const f32x4 &fx4, const f32x4 &fy4,
-                                            int &cmin, int &cmax, int &rmin, int &rmax)
-{
-    FiSite4 g;
-    g.valid = 0;
-    cmin = INT_MAX; cmax = -1; rmin = INT_MAX; rmax = -1;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const FiSite s = fi_locate(x + j, y, W, H, fx4[j], fy4[j]);
-        g.ix[j] = s.ix; g.iy[j] = s.iy; g.a[j] = s.a; g.b[j] = s.b;
-        if (inb && s.valid) {
-            g.valid |= 1u << j;
-            cmin = min(cmin, max(s.ix - 1, 0));  cmax = max(cmax, min(s.ix + 2, W - 1));
-            rmin = min(rmin, max(s.iy - 1, 0));  rmax = max(rmax, min(s.iy + 2, H - 1));
-        }
-    }
+    MEMC_FI_SITES(g, x, y, W, H, inb, fx4, fy4);
+    cmin_ = cmin; cmax_ = cmax; rmin_ = rmin; rmax_ = rmax;
     return g;
 }
-
-// keep the loop-invariant tap splats / LDS addresses / blend weights inside the band and chunk loops (hoisted, they
-// spill: see fi_fwd_tiled_fs4)
-__device__ __forceinline__ void lp_launder(f32x4 (&tp)[16], FiSite4 &g)
-{
-#pragma unroll
-    for (int k = 0; k < 16; k++) asm volatile("" : "+v"(tp[k][0]), "+v"(tp[k][1]), "+v"(tp[k][2]), "+v"(tp[k][3]));
-#pragma unroll
-    for (int j = 0; j < 4; j++) asm volatile("" : "+v"(g.ix[j]), "+v"(g.iy[j]), "+v"(g.a[j]), "+v"(g.b[j]));
-}
+__device__ __forceinline__ void fi_launder_fn(f32x4 (&tp)[16], FiSite4 &g) { MEMC_FI_LAUNDER(tp, g); }
 
 // --------------------------------------------------------------------------------------------------
 // Forward, fs == 4, LDS-tiled: 64 x 16 tiles of 256 lanes, one lane = four consecutive sites of a row, strip walk.
@@ -163,8 +69,7 @@ __global__ __launch_bounds__(256, RAGGED ? 1 : 2) void fi_fwd_lp_tiled(
 #pragma unroll
     for (int k = 0; k < 16; k++) tp[k] = ld4_stream<T>(tap_p + k * s3c);
 
-    int cmin, cmax, rmin, rmax;
-    FiSite4 g = lp_sites(x, y, W, H, inb, fx4, fy4, cmin, cmax, rmin, rmax);
+    MEMC_FI_SITES(g, x, y, W, H, inb, fx4, fy4);
     const BBox box = tile_bbox<LX>(cmin, cmax, rmin, rmax, bb);
     const Bands bands = make_bands<LX>(box);
     const st_t<T> *in_b = in1 + b * s1b;
@@ -187,8 +92,8 @@ __global__ __launch_bounds__(256, RAGGED ? 1 : 2) void fi_fwd_lp_tiled(
             lp_stage_load<3>(rb, sl, plane, s1h, sr);
             lp_stage_store<T, 3>(rb, sl, sr, tile);
             __syncthreads();
-            lp_launder(tp, g);
-            lp_gather(rb, g, tp, sel, W, H, tile, res);
+            MEMC_FI_LAUNDER(tp, g);
+            fi_gather<LX, 3>(rb, g, tp, sel, W, H, tile, res);
         }
         if (inb) {
             if (g.valid != 0xFu) {                         // out-of-range sites copy the input pixel
@@ -228,11 +133,11 @@ __global__ __launch_bounds__(256, RAGGED ? 1 : 2) void fi_fwd_lp_tiled(
                 __syncthreads();
                 // next chunk's rows: in flight while this chunk is gathered (the last iteration re-reads its own chunk)
                 stage_load(c0 + 4 < C ? c0 + 4 : c0);
-                lp_launder(tp, g);
+                MEMC_FI_LAUNDER(tp, g);
                 f32x4 res[4];
 #pragma unroll
                 for (int j = 0; j < 4; j++) res[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                lp_gather(r, g, tp, sel, W, H, tile, res);
+                fi_gather<LX, 4>(r, g, tp, sel, W, H, tile, res);
                 const st_t<T> *plane0 = in_b + c0 * s1c;
                 st_t<T> *o = out_p + c0 * s1c;
                 if (wr & ~g.valid) {                       // out-of-range sites copy the input pixel
@@ -266,7 +171,7 @@ __global__ __launch_bounds__(256, RAGGED ? 1 : 2) void fi_fwd_lp_tiled(
     while (slow) {
         const int j = __ffs(slow) - 1;
         slow &= slow - 1;
-        lp_site_scalar<T, FT>(x + j, y, W, H, C, 4, in_b, s1c, s1h, flow_p + j, s2c, tap_p + j, s3c, out_p + j);
+        fi_site_scalar_lp<T, FT>(x + j, y, W, H, C, 4, in_b, s1c, s1h, flow_p + j, s2c, tap_p + j, s3c, out_p + j);
     }
 }
 
@@ -313,7 +218,7 @@ __global__ __launch_bounds__(256, 2) void fi_blend_lp_tiled(
     auto warp = [&](const st_t<T> *in_b, const st_t<FT> *flow_b, const st_t<T> *filt_b, const f32x4 &fx4, const f32x4 &fy4,
                     f32x4 (&res)[4]) {
         int cmin, cmax, rmin, rmax;
-        FiSite4 g = lp_sites(x, y, W, H, inb, fx4, fy4, cmin, cmax, rmin, rmax);
+        FiSite4 g = fi_sites_fn(x, y, W, H, inb, fx4, fy4, cmin, cmax, rmin, rmax);
         const BBox box = tile_bbox<LX>(cmin, cmax, rmin, rmax, bb);
         const Bands bands = make_bands<LX>(box);
 #pragma unroll
@@ -331,8 +236,8 @@ __global__ __launch_bounds__(256, 2) void fi_blend_lp_tiled(
             lp_stage_load<3>(rb, sl, plane, s1h, sr);
             lp_stage_store<T, 3>(rb, sl, sr, tile);
             __syncthreads();
-            lp_launder(tp, g);
-            lp_gather(rb, g, tp, sel, W, H, tile, res);
+            fi_launder_fn(tp, g);
+            fi_gather<LX, 3>(rb, g, tp, sel, W, H, tile, res);
         }
         if (!inb) return;
         unsigned slow = g.valid & ~done;                   // rare: not coverable within kMaxBands bands
@@ -341,10 +246,11 @@ __global__ __launch_bounds__(256, 2) void fi_blend_lp_tiled(
             slow &= slow - 1;
             const st_t<FT> *fp = flow_b + (int64_t)y * s2h + x + j;
             const FiSite s = fi_locate(x + j, y, W, H, widen<FT>(fp[0]), widen<FT>(fp[s2c]));
+            const int L = s.ix - 1, Tp = s.iy - 1;               // the site's 4 x 4 window
             f32x4 v;
 #pragma unroll 1
             for (int c = 0; c < 3; c++)
-                v[c] = lp_site_chan<T>(s, 4, W, H, in_b + c * s1c, s1h, filt_b + (int64_t)y * s3h + x + j, s3c);
+                v[c] = fi_site_chan<T, int64_t>(s, 4, L, Tp, L + 4, Tp + 4, W, H, in_b + c * s1c, s1h, filt_b + (int64_t)y * s3h + x + j, s3c);
             v[3] = 0.f;
 #pragma unroll
             for (int jj = 0; jj < 4; jj++) res[jj] = jj == j ? v : res[jj];
@@ -395,7 +301,7 @@ __global__ __launch_bounds__(256) void fi_fwd_lp_direct(
     const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
     const int x = tx * kWave + (threadIdx.x & (kWave - 1)), y = ty * 4 + (threadIdx.x / kWave);
     if (x >= W || y >= H) return;
-    lp_site_scalar<T, FT>(x, y, W, H, C, fs, in1 + b * s1b, s1c, s1h, flow + b * s2b + (int64_t)y * s2h + x, s2c,
+    fi_site_scalar_lp<T, FT>(x, y, W, H, C, fs, in1 + b * s1b, s1c, s1h, flow + b * s2b + (int64_t)y * s2h + x, s2c,
                           filt + b * s3b + (int64_t)y * s3h + x, s3c, out + b * s1b + (int64_t)y * s1h + x);
 }
 
@@ -418,9 +324,10 @@ __global__ __launch_bounds__(256) void fi_blend_lp_direct(
     const FiSite s1 = fi_locate(x, y, W, H, widen<FT>(flow1[o2]), widen<FT>(flow1[o2 + s2c]));
     const float oc0 = widen<T>(occ0[oo]), oc1 = widen<T>(occ1[oo]);
     const st_t<T> *i0 = in0 + b * s1b, *i2 = in2 + b * s1b;
+    const int L0 = s0.ix + 1 - fs / 2, T0 = s0.iy + 1 - fs / 2, L1 = s1.ix + 1 - fs / 2, T1 = s1.iy + 1 - fs / 2;   // windows
     for (int c = 0; c < C; c++) {
-        const float w0 = s0.valid ? lp_site_chan<T>(s0, fs, W, H, i0 + c * s1c, s1h, filt0 + o3, s3c) : widen<T>(in0[o1 + c * s1c]);
-        const float w2 = s1.valid ? lp_site_chan<T>(s1, fs, W, H, i2 + c * s1c, s1h, filt1 + o3, s3c) : widen<T>(in2[o1 + c * s1c]);
+        const float w0 = s0.valid ? fi_site_chan<T, int64_t>(s0, fs, L0, T0, L0 + fs, T0 + fs, W, H, i0 + c * s1c, s1h, filt0 + o3, s3c) : widen<T>(in0[o1 + c * s1c]);
+        const float w2 = s1.valid ? fi_site_chan<T, int64_t>(s1, fs, L1, T1, L1 + fs, T1 + fs, W, H, i2 + c * s1c, s1h, filt1 + o3, s3c) : widen<T>(in2[o1 + c * s1c]);
         const float p0 = oc0 * w0, p2 = oc1 * w2;
         out[o1 + c * s1c] = narrow<T>(p0 + p2);
     }
@@ -435,48 +342,6 @@ namespace {
 
 using namespace memc;
 constexpr int kErr = -1;
-
-bool fits_int(const memc_tensor4 *t)
-{
-    for (int i = 0; i < 4; i++)
-        if (t->size[i] < 0 || t->size[i] > INT32_MAX || t->stride[i] < 0 || t->stride[i] > INT32_MAX) return false;
-    return true;
-}
-int64_t numel(const memc_tensor4 *t) { return t->size[0] * t->size[1] * t->size[2] * t->size[3]; }
-// usable descriptor: sizes / strides fit int32, unit w stride, non-null data unless empty (layer_api.cpp)
-bool ok(const memc_tensor4 *t) { return t && fits_int(t) && (t->stride[3] == 1 || t->size[3] <= 1) && (t->data || numel(t) == 0); }
-bool same_shape(const memc_tensor4 *a, const memc_tensor4 *b)
-{
-    return a->size[0] == b->size[0] && a->size[1] == b->size[1] && a->size[2] == b->size[2] && a->size[3] == b->size[3];
-}
-// same b/c/h strides (the kernels index `b` with `a`'s strides); the stride of a size-1 dimension is never used
-bool same_layout(const memc_tensor4 *a, const memc_tensor4 *b)
-{
-    if (!same_shape(a, b)) return false;
-    for (int i = 0; i < 3; i++)
-        if (a->size[i] > 1 && a->stride[i] != b->stride[i]) return false;
-    return true;
-}
-// flow [N, 2, H, W] matching input1 [N, C, H, W] (my_lib_cuda.c:611-617)
-bool flow_matches(const memc_tensor4 *in1, const memc_tensor4 *flow)
-{
-    return flow->size[0] == in1->size[0] && flow->size[1] == 2 && flow->size[2] == in1->size[2] && flow->size[3] == in1->size[3];
-}
-bool taps_match(const memc_tensor4 *in1, const memc_tensor4 *filt)
-{
-    return filt->size[0] == in1->size[0] && filt->size[2] == in1->size[2] && filt->size[3] == in1->size[3];
-}
-bool dtypes_ok(memc_dtype payload, memc_dtype flow)
-{
-    return (payload == MEMC_F16 || payload == MEMC_BF16) && (flow == MEMC_F32 || flow == payload);
-}
-// quads of the tiled kernels: strides of every dimension that is walked a multiple of four elements, 8-byte aligned bases
-bool quad_ok(const memc_tensor4 *t)
-{
-    for (int i = 0; i < 3; i++)
-        if (t->size[i] > 1 && t->stride[i] % 4 != 0) return false;
-    return reinterpret_cast<uintptr_t>(t->data) % 8 == 0;
-}
 
 inline int64_t S(const memc_tensor4 *t, int i) { return t->stride[i]; }
 

@@ -1,4 +1,11 @@
-// memc_fi.hpp -- site geometry shared by the FilterInterpolation kernels (filter_interpolation.hip, fi_bwd_cn.hip).
+// memc_fi.hpp -- the per-site device helpers of every FilterInterpolation kernel, forward and backward, fp32 and half
+// storage (filter_interpolation.hip, fi_bwd_c3.hip, fi_bwd_cn.hip, lp_filter_interpolation.hip, lp_fi_bwd_c3.hip, arms/):
+// the geometry of a lane's four sites, the LDS gather, the one-site paths from global memory.
+//
+// What the fp32 kernels and their half twins share is written ONCE here, as a macro wherever a shared always-inline
+// function would be the same source but not the same machine code in the fp32 libraries (the inlined call changes the
+// compiler's scheduling, vectorisation and contraction choices; tools/isa_diff.py is the check), and as a template over
+// the storage (memc_lp.hpp) wherever it is not.
 #pragma once
 
 #include "memc_tile.hpp"
@@ -24,22 +31,129 @@ __device__ __forceinline__ unsigned fi_covered(const Region &r, const FiSite4 &g
     return m;
 }
 
-// Scalar evaluation of ONE site for channels [0, nch) of `plane0`, everything read from global memory
-// (flow, taps, image): the rare path for sites whose source window is not in the staged LDS region, and the
-// body of the any-filter-size kernel.  Same arithmetic order as the fast path.  P: the storage of the image and the taps
-// (memc_lp.hpp: F32, or F16 / BF16 widened exactly at the load).
-template <class P = F32>
+// Site geometry of the lane's four sites (x .. x + 3 of row y) and the box of their clamped 4 x 4 windows: declares the
+// FiSite4 `g` and cmin, cmax, rmin, rmax (no valid site: INT_MAX / -1) in the enclosing scope.
+#define MEMC_FI_SITES(g, x, y, W, H, inb, fx4, fy4)                                                                   \
+    FiSite4 g;                                                                                                        \
+    g.valid = 0;                                                                                                      \
+    int cmin = INT_MAX, cmax = -1, rmin = INT_MAX, rmax = -1;                                                         \
+    _Pragma("unroll")                                                                                                 \
+    for (int j = 0; j < 4; j++) {                                                                                     \
+        const FiSite s = fi_locate((x) + j, (y), (W), (H), (fx4)[j], (fy4)[j]);                                       \
+        g.ix[j] = s.ix; g.iy[j] = s.iy; g.a[j] = s.a; g.b[j] = s.b;                                                   \
+        if ((inb) && s.valid) {                                                                                       \
+            g.valid |= 1u << j;                                                                                       \
+            cmin = min(cmin, max(s.ix - 1, 0));  cmax = max(cmax, min(s.ix + 2, (W) - 1));                            \
+            rmin = min(rmin, max(s.iy - 1, 0));  rmax = max(rmax, min(s.iy + 2, (H) - 1));                            \
+        }                                                                                                             \
+    }
+
+// Everything a band or chunk body derives from the taps and the site geometry (tap splats for the packed FMAs, 64 LDS
+// addresses, blend weights) is loop-invariant; hoisted out of the loop it needs ~400 more registers than exist and lands
+// in scratch (1.5 KB per lane in fi_fwd_tiled_fs4's chunk loop).  Laundering the inputs through empty asm statements once
+// per iteration keeps that arithmetic inside the loop.
+#define MEMC_FI_LAUNDER(tp, g)                                                                                        \
+    do {                                                                                                              \
+        _Pragma("unroll")                                                                                             \
+        for (int k = 0; k < 16; k++)                                                                                  \
+            asm volatile("" : "+v"((tp)[k][0]), "+v"((tp)[k][1]), "+v"((tp)[k][2]), "+v"((tp)[k][3]));                \
+        _Pragma("unroll")                                                                                             \
+        for (int j = 0; j < 4; j++) asm volatile("" : "+v"((g).ix[j]), "+v"((g).iy[j]), "+v"((g).a[j]), "+v"((g).b[j])); \
+    } while (0)
+
+// Gather + blend of the sites selected by `sel` (bit j) from the staged band; other sites keep their `res`.
+// Branch-free: unselected sites still issue their 16 LDS reads (at pixel 0, harmless).  The LDS image is fp32 pixel
+// quads for every storage (staging widens), so this is the gather of the fp32 and of the half kernels.
+template <int LX, int NCH>
+__device__ __forceinline__ void fi_gather(const Region &r, const FiSite4 &g, const f32x4 (&tp)[16], unsigned sel,
+                                          int W, int H, const f32x4 *tile, f32x4 (&res)[4])
+{
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const bool on = (sel >> j) & 1;
+        int ro[4], co[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            ro[k] = on ? (clampi(g.iy[j] - 1 + k, H - 1) - r.y0) * r.pitch : 0;
+            co[k] = on ? swz_col(clampi(g.ix[j] - 1 + k, W - 1) - r.x0) : 0;
+        }
+        // quadrant sums, row-major inside each quadrant as in the reference (rows 0,1 top; 2,3 bottom)
+        f32x4 TL = {0.f, 0.f, 0.f, 0.f}, TR = TL, BL = TL, BR = TL;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            f32x4 v[4];
+#pragma unroll
+            for (int m = 0; m < 4; m++) v[m] = tile[ro[k] + co[m]];
+            if (k < 2) {
+                TL += v[0] * tp[k * 4 + 0][j];  TL += v[1] * tp[k * 4 + 1][j];
+                TR += v[2] * tp[k * 4 + 2][j];  TR += v[3] * tp[k * 4 + 3][j];
+            } else {
+                BL += v[0] * tp[k * 4 + 0][j];  BL += v[1] * tp[k * 4 + 1][j];
+                BR += v[2] * tp[k * 4 + 2][j];  BR += v[3] * tp[k * 4 + 3][j];
+            }
+        }
+        const float a = g.a[j], bt = g.b[j];
+        const f32x4 val = ((1 - a) * (1 - bt)) * TL + (a * (1 - bt)) * TR + ((1 - a) * bt) * BL + (a * bt) * BR;
+        res[j] = on ? val : res[j];
+    }
+}
+
+// One quadrant sum of one channel of one site, everything read from global memory, any filter size: row-major from 0,
+// the reference's order.  P: the storage of the image and the taps (memc_lp.hpp: F32, or F16 / BF16 widened exactly at
+// the load).  I: the type of a row offset -- int where the C ABI hands the kernels `int` strides or the launcher has
+// checked the plane (every fp32 kernel, the half backward); int64_t in the half forward, whose one-lane-per-site kernel
+// takes any plane.
+template <class P = F32, class I = int>
 __device__ __forceinline__ float fi_quad_sum(const st_t<P> *p, int s1h, int W, int H, const st_t<P> *tap_p,
                                              int64_t s3c, int fs, int L, int T, int j0, int j1, int i0, int i1)
 {
     float acc = 0.0f;
     for (int j = j0; j <= j1; j++) {
-        const int jj = clampi(j, H - 1) * s1h;
+        const I jj = (I)clampi(j, H - 1) * s1h;
         for (int i = i0; i <= i1; i++)
             acc += widen_f32<P>(p[jj + clampi(i, W - 1)]) * widen_f32<P>(tap_p[((j - T) * fs + (i - L)) * s3c]);
     }
     return acc;
 }
+
+// One channel of one valid site from global memory: the four quadrant sums over the site's fs x fs window, columns
+// [L, R) and rows [T, Bm) with L = ix + 1 - fs / 2, T = iy + 1 - fs / 2, then the four-term blend.  The window is the
+// caller's, computed once for all channels and handed over as four ints: as a struct, or computed in here, the fp32
+// callers compile to other machine code.
+template <class P = F32, class I = int>
+__device__ __forceinline__ float fi_site_chan(const FiSite &s, int fs, int L, int T, int R, int Bm, int W, int H,
+                                              const st_t<P> *p, int s1h, const st_t<P> *tap_p, int64_t s3c)
+{
+    const float TL = fi_quad_sum<P, I>(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, L, s.ix);
+    const float TR = fi_quad_sum<P, I>(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, s.ix + 1, R - 1);
+    const float BL = fi_quad_sum<P, I>(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, L, s.ix);
+    const float BR = fi_quad_sum<P, I>(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, s.ix + 1, R - 1);
+    return (1 - s.a) * (1 - s.b) * TL + s.a * (1 - s.b) * TR + (1 - s.a) * s.b * BL + s.a * s.b * BR;
+}
+
+// ONE site of the forward for channels [0, nch) of `plane0`, everything read from global memory (flow, taps, image): the
+// rare path for sites whose source window no staged LDS band covers, and the body of the half library's one-lane-per-site
+// kernel.  Same arithmetic order as the fast path; an out-of-range site copies the input pixel.  FT: the storage of the
+// flow.  A macro body, expanded in fi_site_scalar (filter_interpolation.hip: the fp32 library's named function) and in
+// fi_site_scalar_lp below: behind a forwarding call the fp32 function compiles to other machine code.
+#define MEMC_FI_SITE_SCALAR_BODY(P, FT, I)                                                                            \
+    {                                                                                                                 \
+        const float fx = widen<FT>(flow_p[0]), fy = widen<FT>(flow_p[s2c]);                                           \
+        const FiSite s = fi_locate(x, y, W, H, fx, fy);                                                               \
+        if (s.valid) {                                                                                                \
+            const int L = s.ix + 1 - fs / 2, T = s.iy + 1 - fs / 2, R = L + fs, Bm = T + fs;                          \
+            for (int c = 0; c < nch; c++)                                                                             \
+                out_p[c * s1c] = narrow<P>(fi_site_chan<P, I>(s, fs, L, T, R, Bm, W, H, plane0 + c * s1c, s1h, tap_p, s3c)); \
+        } else {                                                                                                      \
+            const st_t<P> *p = plane0 + (int64_t)y * s1h + x;                                                         \
+            for (int c = 0; c < nch; c++) out_p[c * s1c] = p[c * s1c];                                                \
+        }                                                                                                             \
+    }
+template <class P, class FT>
+__device__ __noinline__ void fi_site_scalar_lp(int x, int y, int W, int H, int nch, int fs, const st_t<P> *plane0,
+                                               int64_t s1c, int s1h, const st_t<FT> *flow_p, int64_t s2c,
+                                               const st_t<P> *tap_p, int64_t s3c, st_t<P> *out_p)
+MEMC_FI_SITE_SCALAR_BODY(P, FT, int64_t)
 
 // The per-site backward helpers below are written once over the storage of their tensors (memc_lp.hpp): P for the image,
 // the taps and the tap gradient, FT for the flow and its gradient, GT for gradoutput; the image gradient is always fp32

@@ -45,12 +45,7 @@ __device__ __forceinline__ void fi_bwd_phase1(const Region &r, unsigned fast, Fi
                                               st_t<FT> *gin2_b, int64_t s2c, unsigned o2, st_t<P> *gin3_b, int64_t s3c,
                                               unsigned o3)
 {
-    // keep tap splats / weights inside the caller's band loop (hoisted, they spill)
-#pragma unroll
-    for (int k = 0; k < 16; k++)
-        asm volatile("" : "+v"(tp[k][0]), "+v"(tp[k][1]), "+v"(tp[k][2]), "+v"(tp[k][3]));
-#pragma unroll
-    for (int j = 0; j < 4; j++) asm volatile("" : "+v"(g.ix[j]), "+v"(g.iy[j]), "+v"(g.a[j]), "+v"(g.b[j]));
+    MEMC_FI_LAUNDER(tp, g);                    // inside the caller's band loop
     // Only quads that this band owns completely (the common case) take this path -- ONE exec-masked region
     // without inner control flow, every store unconditional (the buffers are zero-filled by the caller:
     // 0 + g == g); mixed quads are redone per site by fi_bwd_site_taps.  Any load or data-dependent merge inside
