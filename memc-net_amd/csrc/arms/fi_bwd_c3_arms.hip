@@ -353,48 +353,49 @@ __global__ __launch_bounds__(256, 2) void fi_bwd_tiled_c3_persistent(
     }   // tiles
 }
 
+// The kernels of rounds 1-2 share one argument list: 64 x 16 tiles over the whole width (fi_bwd_c3_launch hands the arms
+// whole widths only), on at most `grid` workgroups.
+template <class K>
+static void launch_fi_bwd_c3_arm(K kernel, unsigned grid, int lds, const FiBwdCall<> &k)
+{
+    using G = TileGeom<16>;
+    const int ntx = (k.w + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH;
+    const unsigned ntiles = (unsigned)ntx * nty * k.batch;
+    hipLaunchKernelGGL(kernel, dim3(grid < ntiles ? grid : ntiles), dim3(256), lds, k.stream, k.w, k.h, ntx, nty, k.batch,
+                       k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.in1, k.flow, k.filt,
+                       k.gout, k.gin1, k.gin2, k.gin3);
+}
+
+// persistent: at most two workgroups per CU
+template <bool PREFETCH>
+static void launch_fi_bwd_tiled_c3_persistent(const FiBwdCall<> &k)
+{
+    const int lds = 2 * AccT::kPlane * 8 + 64;
+    static const bool once = (allow_big_lds(fi_bwd_tiled_c3_persistent<PREFETCH>, lds), true);
+    (void)once;
+    launch_fi_bwd_c3_arm(fi_bwd_tiled_c3_persistent<PREFETCH>, persistent_grid(2), lds, k);
+}
+
 // 1: launched, 0: no such arm, -1: launch error.  Geometry has been checked by fi_bwd_c3_launch.
-int fi_bwd_c3_arm_launch(int variant, hipStream_t stream, int w, int h, int ntx, int nty, int batch,
-                         int s1b, int s1c, int s1h, int s2b, int s2c, int s2h, int s3b, int s3c, int s3h,
-                         const float *input1, const float *input2, const float *input3, const float *gradoutput,
-                         float *gradinput1, float *gradinput2, float *gradinput3)
+int fi_bwd_c3_arm_launch(int variant, const FiBwdCall<> &k)
 {
     using G = TileGeom<16>;
     static_assert(AccT::kPlane * 8 <= G::kCapPx * 16 && G::kPitch <= AccT::kMaxW && G::kRows <= AccT::kRows,
                   "the accumulator plane aliases the staged image");
-    const unsigned ntiles = (unsigned)ntx * nty * batch;
-#define MEMC_FI_BWD_ARGS                                                                                           \
-    w, h, ntx, nty, batch, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b,         \
-        (int64_t)s3c, s3h, input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3
-#define MEMC_FI_BWD(ABL)                                                                                           \
-    hipLaunchKernelGGL(fi_bwd_tiled_c3<ABL>, dim3(ntiles), dim3(256), tile_lds_bytes<16>(), stream, MEMC_FI_BWD_ARGS)
-#define MEMC_FI_BWD_P(PF)                                                                                          \
-    do {                                                                                                           \
-        const int lds = 2 * AccT::kPlane * 8 + 64;                                                                 \
-        static const bool once = (allow_big_lds(fi_bwd_tiled_c3_persistent<PF>, lds), true);                       \
-        (void)once;                                                                                                \
-        const unsigned grid = ntiles < persistent_grid(2) ? ntiles : persistent_grid(2);                           \
-        hipLaunchKernelGGL(fi_bwd_tiled_c3_persistent<PF>, dim3(grid), dim3(256), lds, stream, MEMC_FI_BWD_ARGS);  \
-    } while (0)
+    const auto tiled = [&](auto kernel) { launch_fi_bwd_c3_arm(kernel, UINT_MAX, tile_lds_bytes<16>(), k); };   // one workgroup per tile
     switch (variant) {
-    case 0: MEMC_FI_BWD(0); break;                         // the production kernel of rounds 1-2
-    case 1: MEMC_FI_BWD(1); break;
-    case 2: MEMC_FI_BWD(2); break;
-    case 3: MEMC_FI_BWD(3); break;
-    case 4: MEMC_FI_BWD(4); break;
-    case 5: MEMC_FI_BWD(5); break;
-    case 9: MEMC_FI_BWD(9); break;
-    case 16:                                               // three workgroups per CU: 168 VGPRs, spills
-        hipLaunchKernelGGL((fi_bwd_tiled_c3<0, 3>), dim3(ntiles), dim3(256), tile_lds_bytes<16>(), stream,
-                           MEMC_FI_BWD_ARGS);
-        break;
-    case 10: MEMC_FI_BWD_P(true); break;
-    case 11: MEMC_FI_BWD_P(false); break;
+    case 0: tiled(fi_bwd_tiled_c3<0>); break;             // the production kernel of rounds 1-2
+    case 1: tiled(fi_bwd_tiled_c3<1>); break;
+    case 2: tiled(fi_bwd_tiled_c3<2>); break;
+    case 3: tiled(fi_bwd_tiled_c3<3>); break;
+    case 4: tiled(fi_bwd_tiled_c3<4>); break;
+    case 5: tiled(fi_bwd_tiled_c3<5>); break;
+    case 9: tiled(fi_bwd_tiled_c3<9>); break;
+    case 16: tiled(fi_bwd_tiled_c3<0, 3>); break;         // three workgroups per CU: 168 VGPRs, spills
+    case 10: launch_fi_bwd_tiled_c3_persistent<true>(k); break;
+    case 11: launch_fi_bwd_tiled_c3_persistent<false>(k); break;
     default: return 0;
     }
-#undef MEMC_FI_BWD
-#undef MEMC_FI_BWD_P
-#undef MEMC_FI_BWD_ARGS
     return launch_status() == 0 ? 1 : -1;
 }
 

@@ -35,63 +35,51 @@ __global__ __launch_bounds__(NT, RAG ? 1 : (PART == 0 || !kPartThree ? 2 : 3)) v
 #include "fi_bwd_c3_body.inc"
 }
 
+// The tiles cover the whole quads (sites x < w & ~3): 64 x NT / 16 sites each.
+template <bool TR, int NT = 256, int PART = 0, bool RAG = false>
+static void launch_fi_bwd_c3_pk(const FiBwdCall<> &k)
+{
+    using G = TileGeom<16, 3072, NT>;
+    const int ntx = ((k.w & ~3) + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH;
+    hipLaunchKernelGGL((fi_bwd_c3_pk<TR, NT, PART, RAG>), dim3((unsigned)ntx * nty * k.batch), dim3(NT), PkGeomT<NT>::kLds,
+                       k.stream, k.w, k.h, ntx, nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b,
+                       k.s3.c, k.s3.h, k.in1, k.flow, k.filt, k.gout, k.gin1, k.gin2, k.gin3);
+}
+
 // 1: taken; 2: taken for the whole quads of a ragged width (w % 4 != 0): the caller runs the direct kernel on the columns
 // from w & ~3 on; 0: not taken (the caller takes the direct kernel for everything); -1: launch error.  `variant` >= 0
 // selects a measurement arm (measurement build only; the product passes -1).
-int fi_bwd_c3_launch(hipStream_t stream, int w, int h, int batch,
-                     int s1b, int s1c, int s1h, int s2b, int s2c, int s2h, int s3b, int s3c, int s3h,
-                     const float *input1, const float *input2, const float *input3, const float *gradoutput,
-                     float *gradinput1, float *gradinput2, float *gradinput3, int variant)
+int fi_bwd_c3_launch(const FiBwdCall<> &k, int variant)
 {
-    const int ws = w & ~3;
-    if (!plane_fits_u32(w, h, {s1h, s2h, s3h}) || ws < 4) return 0;
-    if (ws < w && (gradinput1 == nullptr || variant >= 0)) return 0;   // (the tail's direct kernel needs the buffer; arms: whole widths)
-    using G = TileGeom<16>;
-    const int ntx = (ws + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;
-    const unsigned ntiles = (unsigned)ntx * nty * batch;
-#define MEMC_FI_BWD_PK(TR, NT_, NTY, NTILES) MEMC_FI_BWD_PK_PART(TR, NT_, NTY, NTILES, 0)
-#define MEMC_FI_BWD_PK_PART(TR, NT_, NTY, NTILES, PART_)                                                           \
-    hipLaunchKernelGGL((fi_bwd_c3_pk<TR, NT_, PART_>), dim3(NTILES), dim3(NT_), PkGeomT<NT_>::kLds, stream, w, h, ntx, NTY, batch, \
-                       (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b,             \
-                       (int64_t)s3c, s3h, input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3)
+    const int w = k.w, ws = w & ~3;
+    if (!plane_fits_u32(w, k.h, {k.s1.h, k.s2.h, k.s3.h}) || ws < 4) return 0;
+    if (ws < w && (k.gin1 == nullptr || variant >= 0)) return 0;   // (the tail's direct kernel needs the buffer; arms: whole widths)
 #ifdef MEMC_MEASURE
-    bool split = false;                                    // arm 62: the two halves as two launches (LOST, see the kernel)
     if (variant == 28) {                                   // + timestamps
-        MEMC_FI_BWD_PK(true, 256, nty, ntiles);
+        launch_fi_bwd_c3_pk<true>(k);
         return launch_status() == 0 ? 1 : -1;
     }
     if (variant == 61) {                                   // A/B arm: 64 x 8 tiles on 128 lanes (LOST, see PkGeomT)
-        const int nty8 = (h + 7) / 8;
-        MEMC_FI_BWD_PK(false, 128, nty8, (unsigned)ntx * nty8 * batch);
+        launch_fi_bwd_c3_pk<false, 128>(k);
         return launch_status() == 0 ? 1 : -1;
     }
     if (variant >= 0 && variant != 60) {                   // arms/fi_bwd_c3_arms.hip (60: this kernel, named)
-        const int r = fi_bwd_c3_arm_launch(variant, stream, w, h, ntx, nty, batch, s1b, s1c, s1h, s2b, s2c, s2h, s3b, s3c,
-                                           s3h, input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3);
+        const int r = fi_bwd_c3_arm_launch(variant, k);
         if (r != 0) return r;
     }
-    if (variant == 62) split = true;                       // (60: the product kernel, named)
-#else
-    (void)variant;
 #endif
-    if (gradinput1 == nullptr) {                           // the caller does not want the image gradient
-        MEMC_FI_BWD_PK_PART(false, 256, nty, ntiles, 2);
-    }
+    if (k.gin1 == nullptr) {                               // the caller does not want the image gradient
+        launch_fi_bwd_c3_pk<false, 256, 2>(k);
 #ifdef MEMC_MEASURE
-    else if (split) {
-        MEMC_FI_BWD_PK_PART(false, 256, nty, ntiles, 1);
-        MEMC_FI_BWD_PK_PART(false, 256, nty, ntiles, 2);
-    }
+    } else if (variant == 62) {                            // arm: the two halves as two launches (LOST, see the kernel)
+        launch_fi_bwd_c3_pk<false, 256, 1>(k);
+        launch_fi_bwd_c3_pk<false, 256, 2>(k);
 #endif
-    else if (ws < w) {                                     // a ragged width: the RAG instantiation (+ the caller's tail launch)
-        hipLaunchKernelGGL((fi_bwd_c3_pk<false, 256, 0, true>), dim3(ntiles), dim3(256), PkGeomT<256>::kLds, stream, w, h, ntx, nty,
-                           batch, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c,
-                           s3h, input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3);
+    } else if (ws < w) {                                   // a ragged width: the RAG instantiation (+ the caller's tail launch)
+        launch_fi_bwd_c3_pk<false, 256, 0, true>(k);
     } else {
-        MEMC_FI_BWD_PK(false, 256, nty, ntiles);
+        launch_fi_bwd_c3_pk<false>(k);
     }
-#undef MEMC_FI_BWD_PK_PART
-#undef MEMC_FI_BWD_PK
     return launch_status() == 0 ? (ws < w ? 2 : 1) : -1;
 }
 

@@ -807,8 +807,53 @@ __global__ __launch_bounds__(256) void fi_fwd_generic(
     }
 }
 
+// --------------------------------------------------------------------------------------------------
+// Host: one launch function per forward kernel family -- its tile count, grid, LDS bytes and argument list.
+// --------------------------------------------------------------------------------------------------
+// xoff: the tile grid shifted left by this many sites (the kernel's xoff); stripe: the grid rounded up to whole stripes
+// of this many tile columns (WALK 4 to 6).  RAGW: the whole quads of a ragged width.
+template <int LX, int CT, int MINW, int WALK, bool RAGW = false, int CAP = 3072, int PHASE = 0>
+void launch_fi_fwd_tiled_fs4(const FiFwdCall<> &k, int xoff = 0, int stripe = 1)
+{
+    using G = TileGeom<LX, CAP>;
+    const int ws = RAGW ? k.w & ~3 : k.w;
+    const int ntx = (ws + xoff + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH;
+    const unsigned grid = (unsigned)((ntx + stripe - 1) / stripe * stripe) * nty * k.batch;
+    constexpr int lds = tile_lds_bytes<LX, CAP>();
+    allow_big_lds(fi_fwd_tiled_fs4<LX, CT, MINW, WALK, RAGW, CAP, PHASE>, lds);   // per launch: a per-DEVICE attribute
+    hipLaunchKernelGGL((fi_fwd_tiled_fs4<LX, CT, MINW, WALK, RAGW, CAP, PHASE>), dim3(grid), dim3(256), lds, k.stream,
+                       k.w, k.h, k.channel, ntx, nty, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c,
+                       k.s3.h, k.in1, k.flow, k.filt, k.out, xoff);
+}
+
+// The grid is rounded up to whole stripes of SW tile columns (SW 0: strips, nothing to round).
+template <int SW, int NT = 256, bool RAGGED = false, int LX = 16, int ABL = 0, bool RAGW = false>
+void launch_fi_fwd_tiled_c4n(const FiFwdCall<> &k)
+{
+    using G = TileGeom<LX, (NT == 256 ? 3072 : 6144), NT>;
+    const int ws = RAGW ? k.w & ~3 : k.w;
+    const int ntx = (ws + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH;
+    const int lds = G::kCapPx * 16 + 4 * 4 * (NT / 64);
+    allow_big_lds(fi_fwd_tiled_c4n<SW, NT, RAGGED, LX, ABL, RAGW>, lds);          // per launch: a per-DEVICE attribute
+    hipLaunchKernelGGL((fi_fwd_tiled_c4n<SW, NT, RAGGED, LX, ABL, RAGW>),
+                       dim3((unsigned)((ntx + (SW ? SW : 1) - 1) / (SW ? SW : 1) * (SW ? SW : 1)) * nty * k.batch), dim3(NT),
+                       lds, k.stream, k.w, k.h, k.channel, ntx, nty, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h,
+                       k.s3.b, k.s3.c, k.s3.h, k.in1, k.flow, k.filt, k.out);
+}
+
+// x0 == 0: every site; x0 > 0: one tile column from x0 on (the one to three columns behind a ragged width's whole quads).
+template <int CT, int ROWS>
+void launch_fi_fwd_direct_fs4(const FiFwdCall<> &k, int x0 = 0)
+{
+    const int tiles_x = x0 > 0 ? 1 : (k.w + kWave - 1) / kWave, tiles_y = (k.h + ROWS - 1) / ROWS;
+    const unsigned nwg = (unsigned)tiles_x * tiles_y * k.batch;
+    hipLaunchKernelGGL((fi_fwd_direct_fs4<CT, ROWS>), dim3(nwg), dim3(64 * ROWS), 0, k.stream, k.w, k.h, k.channel,
+                       tiles_x, tiles_y, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.in1,
+                       k.flow, k.filt, k.out, x0);
+}
+
 #ifdef MEMC_MEASURE
-#include "arms/fi_fwd_arms.hpp"           // fi_fwd_refshape: measurement build only
+#include "arms/fi_fwd_arms.hpp"           // fi_fwd_refshape, fi_fwd_arm_launch: measurement build only
 #endif
 
 // --------------------------------------------------------------------------------------------------
@@ -916,6 +961,16 @@ __global__ __launch_bounds__(64 * ROWS) void fi_bwd_direct_fs4(
     st_stream(g2 + s2c, boty);
 }
 
+// x0: as launch_fi_fwd_direct_fs4 (the whole quads of a ragged width were fi_bwd_c3_pk's; both ADD into gradinput1)
+template <int CT, int ROWS>
+void launch_fi_bwd_direct_fs4(const FiBwdCall<> &k, int x0 = 0)
+{
+    const int tiles_x = x0 > 0 ? 1 : (k.w + kWave - 1) / kWave, tiles_y = (k.h + ROWS - 1) / ROWS;
+    const unsigned nwg = (unsigned)tiles_x * tiles_y * k.batch;
+    hipLaunchKernelGGL((fi_bwd_direct_fs4<CT, ROWS>), dim3(nwg), dim3(64 * ROWS), 0, k.stream, k.w, k.h, k.channel,
+                       tiles_x, tiles_y, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.in1,
+                       k.flow, k.filt, k.gout, k.gin1, k.gin2, k.gin3, x0);
+}
 
 // Backward, any filter size (rare path; run-time loops).
 __global__ __launch_bounds__(256) void fi_bwd_generic(
@@ -991,9 +1046,9 @@ using namespace memc;
 // Variant selection for A/B measurement (memc_internal.h); -1 = automatic.  Measurement build only: in the product
 // build both are compile-time constants (-1), every `variant == n` branch below folds away and the ablation kernels
 // are never instantiated.  Nothing is read from the environment in either build.
-#ifdef MEMC_MEASURE
 MEMC_KNOB_STATIC(g_fi_fwd_variant, -1);
 MEMC_KNOB_STATIC(g_fi_bwd_variant, -1);
+#ifdef MEMC_MEASURE
 extern "C" void memc_debug_set_fi_fwd_variant(int v) { g_fi_fwd_variant = v; }
 extern "C" void memc_debug_set_fi_phase(int per_win)          // period * 65536 + window, ticks of 10 ns (arm 26)
 {
@@ -1011,172 +1066,34 @@ extern "C" int FilterInterpolationLayer_gpu_forward_kernel(
     const float *input1, const float *input2, const float *input3, float *output)
 {
     (void)nElement; (void)s1w; (void)s2w; (void)s3w;
-    hipStream_t stream = (hipStream_t)stream_;
     if (w <= 0 || h <= 0 || channel <= 0 || batch <= 0) return 0;
+    const FiFwdCall<> k = {(hipStream_t)stream_, w, h, channel, batch, filter_size, plane(s1b, s1c, s1h),
+                           plane(s2b, s2c, s2h), plane(s3b, s3c, s3h), input1, input2, input3, output};
     // production path: LDS-tiled, 16 B per lane (needs 4-element-aligned geometry)
     const bool vec = vec4_ok(w, {s1b, s1c, s1h, s2b, s2c, s2h, s3b, s3c, s3h}, {input1, input2, input3, output});
-#define MEMC_FI_TILED(LX, CT, MINW)   MEMC_FI_TILED_X(LX, CT, MINW, 0, 0)
-#define MEMC_FI_TILED_A(LX, CT, MINW, WALK) MEMC_FI_TILED_X(LX, CT, MINW, WALK, 0)
-#define MEMC_FI_TILED_X(LX, CT, MINW, WALK, XOFF)                                                               \
-    do {                                                                                                   \
-        using G = TileGeom<LX>;                                                                            \
-        const int ntx = (w + (XOFF) + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;               \
-        hipLaunchKernelGGL((fi_fwd_tiled_fs4<LX, CT, MINW, WALK>), dim3((unsigned)ntx * nty * batch), dim3(256), \
-                           tile_lds_bytes<LX>(), stream, w, h, channel, ntx, nty, (int64_t)s1b,            \
-                           (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, \
-                           s3h, input1, input2, input3, output, XOFF);                                      \
-    } while (0)
-#define MEMC_FI_C4N(SW) MEMC_FI_C4N_NT(SW, 256, false)
-#define MEMC_FI_C4N_NT(SW, NT, RAG) MEMC_FI_C4N_LX(SW, NT, RAG, 16)
-#define MEMC_FI_C4N_LX(SW, NT, RAG, LX) MEMC_FI_C4N_ABL(SW, NT, RAG, LX, 0)
-#define MEMC_FI_C4N_ABL(SW, NT, RAG, LX, ABL)                                                                   \
-    do {                                                                                                   \
-        using G = TileGeom<LX, (NT == 256 ? 3072 : 6144), NT>;                                             \
-        const int ntx = (w + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;                        \
-        const int lds = G::kCapPx * 16 + 4 * 4 * (NT / 64);                                                \
-        allow_big_lds(fi_fwd_tiled_c4n<SW, NT, RAG, LX, ABL>, lds);   /* per launch: a per-DEVICE attribute */ \
-        hipLaunchKernelGGL((fi_fwd_tiled_c4n<SW, NT, RAG, LX, ABL>), dim3((unsigned)((ntx + (SW ? SW : 1) - 1) / (SW ? SW : 1) * \
-                                                                    (SW ? SW : 1)) * nty * batch),          \
-                           dim3(NT), lds, stream, w, h, channel, ntx, nty, (int64_t)s1b,                   \
-                           (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c,    \
-                           s3h, input1, input2, input3, output);                                           \
-    } while (0)
-#define MEMC_FI_FWD_LAUNCH(CT, ROWS)                                                                       \
-    do {                                                                                                   \
-        const int tiles_x = (w + kWave - 1) / kWave, tiles_y = (h + (ROWS) - 1) / (ROWS);                  \
-        const unsigned nwg = (unsigned)tiles_x * tiles_y * batch;                                          \
-        hipLaunchKernelGGL((fi_fwd_direct_fs4<CT, ROWS>), dim3(nwg), dim3(64 * (ROWS)), 0, stream, w, h,   \
-                           channel, tiles_x, tiles_y, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b,       \
-                           (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3,     \
-                           output, 0);                                                                     \
-    } while (0)
-
+    const bool arm = g_fi_fwd_variant >= 0;                // a measurement arm is selected (never in the product build)
 #ifdef MEMC_MEASURE
-#define MEMC_FI_FWD_NO_ARM && g_fi_fwd_variant < 0
-#else
-#define MEMC_FI_FWD_NO_ARM
+    if (arm) {                                             // arms/fi_fwd_arms.hpp; an arm that does not take the shape falls through
+        const int r = fi_fwd_arm_launch(g_fi_fwd_variant, k, vec);
+        if (r != 0) return r > 0 ? 0 : -1;
+    }
 #endif
-#ifdef MEMC_MEASURE
-    // ---- measurement build only: A/B and ablation arms (tools/bench_ops.py); several return WRONG results ----
-    const int variant = g_fi_fwd_variant;
-    if (variant == 0) {  // reference-structure measurement arm
-        dim3 block(32, 16, 1), grid((w + 31) / 32, (h + 15) / 16, batch);
-        hipLaunchKernelGGL(fi_fwd_refshape, grid, block, 0, stream, w, h, channel, filter_size,
-                           (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h,
-                           (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output);
-        return launch_status();
-    }
-    if (filter_size == 4 && variant >= 1 && variant <= 3) {       // force the scalar direct-gather kernels
-        if (channel == 3) {
-            if (variant == 2) MEMC_FI_FWD_LAUNCH(3, 8);
-            else if (variant == 3) MEMC_FI_FWD_LAUNCH(3, 2);
-            else MEMC_FI_FWD_LAUNCH(3, 4);
-        } else {
-            if (variant == 2) MEMC_FI_FWD_LAUNCH(0, 8);
-            else if (variant == 3) MEMC_FI_FWD_LAUNCH(0, 2);
-            else MEMC_FI_FWD_LAUNCH(0, 4);
-        }
-        return launch_status();
-    }
-    if (filter_size == 4 && vec && variant >= 4) {
-        bool handled = true;
-        if (variant == 5) {
-            if (channel == 3) MEMC_FI_TILED(8, 3, 3); else MEMC_FI_TILED(8, 0, 3);
-        } else if (variant == 6) {
-            if (channel == 3) MEMC_FI_TILED(16, 3, 2); else MEMC_FI_TILED(16, 0, 2);
-        } else if (variant == 7) {
-            if (channel == 3) MEMC_FI_TILED(8, 3, 2); else MEMC_FI_TILED(8, 0, 2);
-        } else if (variant == 4) {
-            if (channel == 3) MEMC_FI_TILED(16, 3, 3); else MEMC_FI_TILED(16, 0, 3);
-        } else if (variant == 8 && channel == 3) {
-            MEMC_FI_TILED_A(16, 3, 2, 1);
-        } else if (variant == 11 && channel == 3) {
-            MEMC_FI_TILED_A(16, 3, 3, 4);
-        } else if ((variant == 15 || variant == 16 || variant == 17) && channel == 3) {
-            using G = TileGeom<16>;
-            const int ntx = (w + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;
-            const int sw = variant == 15 ? 2 : 4;
-            const unsigned grid = (unsigned)((ntx + sw - 1) / sw * sw) * nty * batch;
-#define MEMC_FI_STRIPE(WALK, MINW)                                                                             \
-            hipLaunchKernelGGL((fi_fwd_tiled_fs4<16, 3, MINW, WALK>), dim3(grid), dim3(256), tile_lds_bytes<16>(), \
-                               stream, w, h, channel, ntx, nty, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b,     \
-                               (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output, 0)
-            if (variant == 15) MEMC_FI_STRIPE(5, 2);
-            else if (variant == 16) MEMC_FI_STRIPE(6, 2);
-            else MEMC_FI_STRIPE(4, 2);                     // 17: row-major chunk per XCD at 2 waves/SIMD
-#undef MEMC_FI_STRIPE
-        } else if (variant == 26 && channel == 3) {       // the product kernel with phased stores (memc_debug_set_fi_phase)
-            using G = TileGeom<16>;
-            const int ntx = (w + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;
-            hipLaunchKernelGGL((fi_fwd_tiled_fs4<16, 3, 2, 0, false, 3072, 1>), dim3((unsigned)ntx * nty * batch), dim3(256),
-                               tile_lds_bytes<16>(), stream, w, h, channel, ntx, nty, (int64_t)s1b, (int64_t)s1c, s1h,
-                               (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output, 0);
-        } else if (variant >= 20 && variant <= 25 && channel == 3) {
-            // 20: 128 x 8 tiles (LX = 32) with a 4608-pixel budget, strips; 21: the same in hardware order; 22: 64 x 16 tiles
-            // with a 4096-pixel budget (no band sweeps on i.i.d. flow); 23: 128 x 8 tiles on the product's 3072 pixels; 24 / 25:
-            // 128 x 8 tiles on 3392 pixels (53 KiB: the most that leaves three workgroups per CU), registers for two / three
-#define MEMC_FI_WIDE(LX, WALK, CAP) MEMC_FI_WIDE_M(LX, WALK, CAP, 2)
-#define MEMC_FI_WIDE_M(LX, WALK, CAP, MINW)                                                                             \
-            do {                                                                                                  \
-                using G = TileGeom<LX, CAP>;                                                                      \
-                const int ntx = (w + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;                       \
-                allow_big_lds(fi_fwd_tiled_fs4<LX, 3, MINW, WALK, false, CAP>, tile_lds_bytes<LX, CAP>());        \
-                hipLaunchKernelGGL((fi_fwd_tiled_fs4<LX, 3, MINW, WALK, false, CAP>), dim3((unsigned)ntx * nty * batch), \
-                                   dim3(256), (tile_lds_bytes<LX, CAP>()), stream, w, h, channel, ntx, nty,       \
-                                   (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h,              \
-                                   (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output, 0);           \
-            } while (0)
-            if (variant == 20) MEMC_FI_WIDE(32, 0, 4608);
-            else if (variant == 21) MEMC_FI_WIDE(32, 1, 4608);
-            else if (variant == 22) MEMC_FI_WIDE(16, 0, 4096);
-            else if (variant == 23) MEMC_FI_WIDE(32, 0, 3072);
-            else if (variant == 24) MEMC_FI_WIDE(32, 0, 3392);
-            else MEMC_FI_WIDE_M(32, 0, 3392, 3);
-#undef MEMC_FI_WIDE
-#undef MEMC_FI_WIDE_M
-        } else if (variant == 30 && channel % 4 == 0 && channel >= 8) {
-            MEMC_FI_C4N(2);
-        } else if (variant == 31 && channel % 4 == 0 && channel >= 8) {
-            MEMC_FI_C4N(4);
-        } else if (variant == 32 && channel % 4 == 0 && channel >= 8) {
-            MEMC_FI_C4N_NT(0, 512, false);                 // 64 x 32 tiles, 512 lanes
-        } else if (variant == 35 && channel % 4 == 0 && channel >= 8) {
-            MEMC_FI_C4N_NT(4, 512, false);                 // ... in stripes four tile columns wide
-        } else if (variant == 36 && channel % 4 == 0 && channel >= 8) {
-            MEMC_FI_C4N_ABL(0, 256, false, 16, 1);         // timing: no gathers
-        } else if (variant == 37 && channel % 4 == 0 && channel >= 8) {
-            MEMC_FI_C4N_ABL(0, 256, false, 16, 2);         // timing: no image loads after the first chunk
-        } else if (variant == 38 && channel % 4 == 0 && channel >= 8) {
-            MEMC_FI_C4N_ABL(0, 512, false, 16, 1);
-        } else if (variant == 39 && channel % 4 == 0 && channel >= 8) {
-            MEMC_FI_C4N_ABL(0, 512, false, 16, 2);
-        } else if (variant == 33 && channel % 4 == 0 && channel >= 8) {
-            MEMC_FI_C4N_LX(0, 256, false, 8);              // 32 x 32 tiles: the box of a square tile is the least dilated
-        } else if (variant == 34 && channel % 4 == 0 && channel >= 8) {
-            MEMC_FI_C4N_LX(4, 256, false, 8);              // ... in stripes four tile columns wide
-        } else {
-            handled = false;
-        }
-        if (handled) return launch_status();
-    }
-#endif  // MEMC_MEASURE
 
     if (filter_size == 4 && vec) {
         if (channel % 4 == 0 && channel >= 8) {                        // e.g. the 64-channel context warp
             MEMC_PATH("fi_fwd:tiled_c4n");
-            MEMC_FI_C4N(0);
+            launch_fi_fwd_tiled_c4n<0>(k);
         } else if (channel == 3) {                                     // default: 64x16 tiles, strip walk
             MEMC_PATH("fi_fwd:tiled_c3");
             // rows of a multiple of 1 KiB (720p, 4K): the tile grid shifted 32 sites left, 8 slots of 256 B per workgroup
             // instead of 4 (fi_fwd_tiled_fs4: xoff).  From the strides the kernel is handed, not from the width: views are taken.
-            if (s1h % 256 == 0 && s3h % 256 == 0) MEMC_FI_TILED_X(16, 3, 2, 0, 32);
-            else MEMC_FI_TILED(16, 3, 2);
+            launch_fi_fwd_tiled_fs4<16, 3, 2, 0>(k, s1h % 256 == 0 && s3h % 256 == 0 ? 32 : 0);
         } else if (channel >= 4) {                                     // any other count from four up: the same pipeline,
             MEMC_PATH("fi_fwd:tiled_c4n_ragged");                      // ragged last chunk
-            MEMC_FI_C4N_NT(0, 256, true);
+            launch_fi_fwd_tiled_c4n<0, 256, true>(k);
         } else {
             MEMC_PATH("fi_fwd:tiled_chunks");
-            MEMC_FI_TILED(16, 0, 2);
+            launch_fi_fwd_tiled_fs4<16, 0, 2, 0>(k);
         }
         return launch_status();
     }
@@ -1184,58 +1101,32 @@ extern "C" int FilterInterpolationLayer_gpu_forward_kernel(
         const int tiles_x = (w + kWave - 1) / kWave, tiles_y = (h + 3) / 4;
         const unsigned nwg = (unsigned)tiles_x * tiles_y * batch;
         MEMC_PATH("fi_fwd:generic");
-        hipLaunchKernelGGL(fi_fwd_generic, dim3(nwg), dim3(256), 0, stream, w, h, channel, filter_size,
-                           tiles_x, tiles_y, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h,
-                           (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output);
+        hipLaunchKernelGGL(fi_fwd_generic, dim3(nwg), dim3(256), 0, k.stream, w, h, channel, filter_size, tiles_x, tiles_y,
+                           k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h, input1, input2, input3,
+                           output);
         return launch_status();
     }
     // A width that is not a multiple of four (round 5): the tiled kernel takes the whole quads (sites x < ws), the one-lane-
     // per-site kernel the one to three columns behind them.
     const int ws = w & ~3;
-    if (filter_size == 4 && !vec && ws >= 8 MEMC_FI_FWD_NO_ARM) {
-        using G = TileGeom<16>;
-        const int ntx = (ws + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;
-        const int tail_y = (h + 3) / 4;
+    if (!vec && ws >= 8 && !arm) {
         MEMC_PATH(channel == 3 ? "fi_fwd:tiled_c3" : channel >= 4 ? "fi_fwd:tiled_c4n_ragged" : "fi_fwd:tiled_chunks");
-#define MEMC_FI_TILED_RAGW(CT)                                                                                  \
-        hipLaunchKernelGGL((fi_fwd_tiled_fs4<16, CT, 2, 0, true>), dim3((unsigned)ntx * nty * batch), dim3(256),    \
-                           tile_lds_bytes<16>(), stream, w, h, channel, ntx, nty, (int64_t)s1b, (int64_t)s1c, s1h,   \
-                           (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output, 0)
-#define MEMC_FI_TAIL(CT)                                                                                        \
-        hipLaunchKernelGGL((fi_fwd_direct_fs4<CT, 4>), dim3((unsigned)tail_y * batch), dim3(256), 0, stream, w, h,  \
-                           channel, 1, tail_y, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h,     \
-                           (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output, ws)
         if (channel >= 4) {                    // the chunk pipeline's any-channel-count instantiation, ragged rows
-            using G4 = TileGeom<16, 3072, 256>;
-            const int lds = G4::kCapPx * 16 + 4 * 4 * (256 / 64);
-            allow_big_lds(fi_fwd_tiled_c4n<0, 256, true, 16, 0, true>, lds);
-            hipLaunchKernelGGL((fi_fwd_tiled_c4n<0, 256, true, 16, 0, true>), dim3((unsigned)ntx * nty * batch), dim3(256), lds,
-                               stream, w, h, channel, ntx, nty, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h,
-                               (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, output);
-            MEMC_FI_TAIL(0);
+            launch_fi_fwd_tiled_c4n<0, 256, true, 16, 0, true>(k);
+            launch_fi_fwd_direct_fs4<0, 4>(k, ws);
         } else if (channel == 3) {
-            MEMC_FI_TILED_RAGW(3);
-            MEMC_FI_TAIL(3);
+            launch_fi_fwd_tiled_fs4<16, 3, 2, 0, true>(k);
+            launch_fi_fwd_direct_fs4<3, 4>(k, ws);
         } else {
-            MEMC_FI_TILED_RAGW(0);
-            MEMC_FI_TAIL(0);
+            launch_fi_fwd_tiled_fs4<16, 0, 2, 0, true>(k);
+            launch_fi_fwd_direct_fs4<0, 4>(k, ws);
         }
-#undef MEMC_FI_TILED_RAGW
-#undef MEMC_FI_TAIL
         return launch_status();
     }
     // everything else: the one-lane-per-site kernels
     MEMC_PATH("fi_fwd:direct");
-    if (channel == 3) MEMC_FI_FWD_LAUNCH(3, 4);
-    else MEMC_FI_FWD_LAUNCH(0, 4);
-#undef MEMC_FI_FWD_LAUNCH
-#undef MEMC_FI_FWD_NO_ARM
-#undef MEMC_FI_C4N
-#undef MEMC_FI_C4N_NT
-#undef MEMC_FI_C4N_LX
-#undef MEMC_FI_TILED
-#undef MEMC_FI_TILED_A
-#undef MEMC_FI_TILED_X
+    if (channel == 3) launch_fi_fwd_direct_fs4<3, 4>(k);
+    else launch_fi_fwd_direct_fs4<0, 4>(k);
     return launch_status();
 }
 
@@ -1251,39 +1142,25 @@ extern "C" int FilterInterpolationLayer_gpu_backward_kernel(
     (void)nElement; (void)s1w; (void)s2w; (void)s3w;
     hipStream_t stream = (hipStream_t)stream_;
     if (w <= 0 || h <= 0 || channel <= 0 || batch <= 0) return 0;
-    const int tiles_x = (w + kWave - 1) / kWave;
-    const int tiles_y = (h + 3) / 4;
-    const unsigned nwg = (unsigned)tiles_x * tiles_y * batch;
+    const FiBwdCall<> k = {stream, w, h, channel, batch, filter_size, plane(s1b, s1c, s1h), plane(s2b, s2c, s2h),
+                           plane(s3b, s3c, s3h), input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3};
     int taken = 0;
     // EXTENSION: gradinput1 == NULL ("the image gradient is not wanted", include/memc_warp.h) is served by the RGB tiled
     // kernel only; every other shape returns -1 and the caller passes a buffer
     if (gradinput1 == nullptr && (filter_size != 4 || channel != 3)) return -1;
-#ifdef MEMC_MEASURE
-    const bool direct_only = g_fi_bwd_variant == 40;       // A/B: the direct kernel (global atomics) for any channel count
-#else
-    constexpr bool direct_only = false;
-#endif
+    const int variant = g_fi_bwd_variant;                  // a measurement arm; -1, a constant, in the product build
+    const bool direct_only = variant == 40;                // A/B: the direct kernel (global atomics) for any channel count
     if (filter_size != 4) {
+        const int tiles_x = (w + kWave - 1) / kWave, tiles_y = (h + 3) / 4;
+        const unsigned nwg = (unsigned)tiles_x * tiles_y * batch;
         MEMC_PATH("fi_bwd:generic");
-        hipLaunchKernelGGL(fi_bwd_generic, dim3(nwg), dim3(256), 0, stream, w, h, channel, filter_size,
-                           tiles_x, tiles_y, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h,
-                           (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, gradoutput,
-                           gradinput1, gradinput2, gradinput3);
-    } else if (channel == 3 &&
-               (taken = fi_bwd_c3_launch(stream, w, h, batch, s1b, s1c, s1h, s2b, s2c, s2h, s3b, s3c, s3h, input1, input2,
-                                         input3, gradoutput, gradinput1, gradinput2, gradinput3,
-#ifdef MEMC_MEASURE
-                                         g_fi_bwd_variant
-#else
-                                         -1
-#endif
-                                         )) != 0) {
+        hipLaunchKernelGGL(fi_bwd_generic, dim3(nwg), dim3(256), 0, stream, w, h, channel, filter_size, tiles_x, tiles_y,
+                           k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h, input1, input2, input3,
+                           gradoutput, gradinput1, gradinput2, gradinput3);
+    } else if (channel == 3 && (taken = fi_bwd_c3_launch(k, variant)) != 0) {
         MEMC_PATH("fi_bwd:tiled_c3");
         if (taken == 2) {                                  // a ragged width: the columns behind the whole quads (both ADD into gradinput1)
-            const int ws = w & ~3, tail_y = (h + 3) / 4;
-            hipLaunchKernelGGL((fi_bwd_direct_fs4<3, 4>), dim3((unsigned)tail_y * batch), dim3(256), 0, stream, w, h, channel, 1,
-                               tail_y, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b,
-                               (int64_t)s3c, s3h, input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3, ws);
+            launch_fi_bwd_direct_fs4<3, 4>(k, w & ~3);
             return launch_status();
         }
         return taken > 0 ? 0 : -1;                         // RGB: fi_bwd_c3.hip
@@ -1296,16 +1173,10 @@ extern "C" int FilterInterpolationLayer_gpu_backward_kernel(
     } else if (channel == 3) {
         if (gradinput1 == nullptr) return -1;              // (unaligned geometry: the direct kernel needs the buffer)
         MEMC_PATH("fi_bwd:direct");
-        hipLaunchKernelGGL((fi_bwd_direct_fs4<3, 4>), dim3(nwg), dim3(256), 0, stream, w, h, channel,
-                           tiles_x, tiles_y, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h,
-                           (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, gradoutput,
-                           gradinput1, gradinput2, gradinput3, 0);
+        launch_fi_bwd_direct_fs4<3, 4>(k);
     } else {
         MEMC_PATH("fi_bwd:direct");
-        hipLaunchKernelGGL((fi_bwd_direct_fs4<0, 4>), dim3(nwg), dim3(256), 0, stream, w, h, channel,
-                           tiles_x, tiles_y, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h,
-                           (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, gradoutput,
-                           gradinput1, gradinput2, gradinput3, 0);
+        launch_fi_bwd_direct_fs4<0, 4>(k);
     }
     return launch_status();
 }
@@ -1328,12 +1199,12 @@ extern "C" int FilterInterpolationBlend_gpu_forward_kernel(
                  {input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1, output}) ||
         !plane_fits_u32(w, h, {s1h, s2h, s3h, soh}))
         return -1;
+    const Plane s1 = plane(s1b, s1c, s1h), s2 = plane(s2b, s2c, s2h), s3 = plane(s3b, s3c, s3h), so = plane(sob, 0, soh);
     using G = TileGeom<16>;
     const int ntx = (w + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;
     hipLaunchKernelGGL(fi_fwd_blend_c3, dim3((unsigned)ntx * nty * batch), dim3(256), tile_lds_bytes<16>(), stream, w,
-                       h, ntx, nty, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b,
-                       (int64_t)s3c, s3h, (int64_t)sob, soh, input0, input2, flow0, flow1, filter0, filter1,
-                       occlusion0, occlusion1, output);
+                       h, ntx, nty, s1.b, s1.c, s1.h, s2.b, s2.c, s2.h, s3.b, s3.c, s3.h, so.b, so.h, input0, input2,
+                       flow0, flow1, filter0, filter1, occlusion0, occlusion1, output);
     return launch_status();
 }
 
@@ -1359,15 +1230,16 @@ extern "C" int FilterInterpolationCtx_gpu_forward_kernel(
                  {image, context, flow, filter, prev, occlusion_prev, occlusion_this, image_out, context_out}))
         return -1;
     if (!plane_fits_u32(w, h, {sih, blend ? soh : 0})) return -1;
+    const Plane si = plane(sib, sic, sih), s1 = plane(s1b, s1c, s1h), s2 = plane(s2b, s2c, s2h), s3 = plane(s3b, s3c, s3h),
+                so = plane(sob, 0, soh);
     using G = TileGeom<16>;
     const int ntx = (w + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;
-#define MEMC_FI_CTX(BLEND)                                                                                       \
-    hipLaunchKernelGGL(fi_fwd_ctx_img<BLEND>, dim3((unsigned)ntx * nty * batch), dim3(256), tile_lds_bytes<16>(), stream, \
-                       w, h, channel, ntx, nty, (int64_t)sib, (int64_t)sic, sih, (int64_t)s1b, (int64_t)s1c, s1h,       \
-                       (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, s3h, (int64_t)sob, soh, image,      \
-                       context, flow, filter, prev, occlusion_prev, occlusion_this, image_out, context_out)
-    if (blend) MEMC_FI_CTX(true);
-    else MEMC_FI_CTX(false);
-#undef MEMC_FI_CTX
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)ntx * nty * batch), dim3(256), tile_lds_bytes<16>(), stream, w, h, channel,
+                           ntx, nty, si.b, si.c, si.h, s1.b, s1.c, s1.h, s2.b, s2.c, s2.h, s3.b, s3.c, s3.h, so.b, so.h,
+                           image, context, flow, filter, prev, occlusion_prev, occlusion_this, image_out, context_out);
+    };
+    if (blend) launch(fi_fwd_ctx_img<true>);
+    else launch(fi_fwd_ctx_img<false>);
     return launch_status();
 }

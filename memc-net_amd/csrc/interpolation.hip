@@ -412,161 +412,145 @@ __global__ __launch_bounds__(NT, NT == 256 && CAP == 3072 ? 3 : 4) void bl_bwd_c
     }
 }
 
-static int launch_bl_fwd(hipStream_t stream, int w, int h, int channel, int batch, int s1b, int s1c, int s1h,
-                         int s2b, int s2c, int s2h, const float *input1, const float *input2, float *output)
+// --------------------------------------------------------------------------------------------------
+// Host: one launch function per kernel family -- its tile count, grid, LDS bytes and argument list.  The tiled kernels
+// serve the whole quads (sites x < w & ~3) of any width, in their RAG instantiation where the width is ragged (w % 4 != 0,
+// round 5); the one-lane-per-site kernels then take the one to three columns behind them (x0 = w & ~3).
+// --------------------------------------------------------------------------------------------------
+inline int bl_stripe() { return g_tile_walk_sw >= 0 ? g_tile_walk_sw : kDefaultStripe; }
+
+template <int CT, int CAP>
+static void launch_bl_fwd_tiled(const BlFwdCall &k)
 {
-    if (w <= 0 || h <= 0 || channel <= 0 || batch <= 0) return 0;
-    // A width that is not a multiple of four (round 5): the tiled kernel takes the whole quads (sites x < ws), the one-lane-
-    // per-site kernel the one to three columns behind them.
+    using G = TileGeom<16, CAP>;
+    const int ws = k.w & ~3, sw = bl_stripe();
+    const int ntx = (ws + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH;
+    const auto kernel = ws < k.w ? bl_fwd_tiled<CT, CAP, true> : bl_fwd_tiled<CT, CAP, false>;
+    hipLaunchKernelGGL(kernel, dim3(walk_grid(ntx, nty, k.batch, sw)), dim3(256), (tile_lds_bytes<16, CAP>() + g_extra_lds),
+                       k.stream, k.w, k.h, k.channel, ntx, nty, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.in1,
+                       k.flow, k.out, sw);
+}
+
+// x0 == 0: every site; x0 > 0: one tile column from x0 on
+template <int CT>
+static void launch_bl_fwd_direct(const BlFwdCall &k, int x0 = 0)
+{
+    const int tiles_x = x0 > 0 ? 1 : (k.w + kWave - 1) / kWave, tiles_y = (k.h + 3) / 4;
+    hipLaunchKernelGGL(bl_fwd<CT>, dim3((unsigned)tiles_x * tiles_y * k.batch), dim3(256), 0, k.stream, k.w, k.h, k.channel,
+                       tiles_x, tiles_y, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.in1, k.flow, k.out, x0);
+}
+
+#ifdef MEMC_MEASURE
+template <int CAP>                             // the fp64-plane kernel of rounds 1-2 (arms/bl_bwd_arms.hpp): whole widths only
+static void launch_bl_bwd_tiled_c3(const BlBwdCall &k)
+{
+    using G = TileGeom<16, CAP>;
+    const int ntx = (k.w + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH, sw = bl_stripe();
+    hipLaunchKernelGGL(bl_bwd_tiled_c3<CAP>, dim3(walk_grid(ntx, nty, k.batch, sw)), dim3(256), (tile_lds_bytes<16, CAP>()),
+                       k.stream, k.w, k.h, ntx, nty, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.in1, k.flow, k.gout,
+                       k.gin1, k.gin2, sw);
+}
+#endif
+
+template <int CAP, int NT>
+static void launch_bl_bwd_c3_pk(const BlBwdCall &k)
+{
+    using G = TileGeom<16, CAP, NT>;
+    constexpr size_t lds = CAP * 16 + 32 * (NT / kWave);    // image or planes; 32 bytes per wave: box, bounds
+    const int ws = k.w & ~3, sw = bl_stripe();
+    const int ntx = (ws + G::kTW - 1) / G::kTW, nty = (k.h + NT / 16 - 1) / (NT / 16);
+    const auto kernel = ws < k.w ? bl_bwd_c3_pk<CAP, NT, true> : bl_bwd_c3_pk<CAP, NT, false>;
+    allow_big_lds(kernel, lds);                // per launch: the attribute belongs to the CURRENT device
+    hipLaunchKernelGGL(kernel, dim3(walk_grid(ntx, nty, k.batch, sw)), dim3(NT), lds, k.stream, k.w, k.h, ntx, nty, k.s1.b,
+                       k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.in1, k.flow, k.gout, k.gin1, k.gin2, sw);
+}
+
+template <int CT>
+static void launch_bl_bwd_direct(const BlBwdCall &k, int x0 = 0)
+{
+    const int tiles_x = x0 > 0 ? 1 : (k.w + kWave - 1) / kWave, tiles_y = (k.h + 3) / 4;
+    hipLaunchKernelGGL(bl_bwd<CT>, dim3((unsigned)tiles_x * tiles_y * k.batch), dim3(256), 0, k.stream, k.w, k.h, k.channel,
+                       tiles_x, tiles_y, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.in1, k.flow, k.gout, k.gin1,
+                       k.gin2, x0);
+}
+
+static int launch_bl_fwd(const BlFwdCall &k)
+{
+    const int w = k.w, channel = k.channel;
+    if (w <= 0 || k.h <= 0 || channel <= 0 || k.batch <= 0) return 0;
     const int ws = w & ~3;
-    const int tail_y = (h + 3) / 4;
     if (ws >= 4) {
-        using G = TileGeom<16>;
-        const int ntx = (ws + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;
-        const int sw = g_tile_walk_sw >= 0 ? g_tile_walk_sw : kDefaultStripe;
         MEMC_PATH(channel == 3 ? "bl_fwd:tiled_c3" : "bl_fwd:tiled_chunks");
-#define MEMC_BL_FWD_R(CT, CAP, RAG)                                                                             \
-            hipLaunchKernelGGL((bl_fwd_tiled<CT, CAP, RAG>), dim3(walk_grid(ntx, nty, batch, sw)), dim3(256),       \
-                               (tile_lds_bytes<16, CAP>() + g_extra_lds), stream, w, h, channel, ntx, nty, (int64_t)s1b, \
-                               (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, input1, input2, output, sw)
-#define MEMC_BL_FWD(CT, CAP)                                                                                    \
-            do {                                                                                                    \
-                if (ws < w) MEMC_BL_FWD_R(CT, CAP, true);                                                           \
-                else MEMC_BL_FWD_R(CT, CAP, false);                                                                 \
-            } while (0)
         if (channel == 3) {
             // 39 KiB instead of 48: 4 workgroups per CU.  The kernel is bound by the latency of a tile's serial chain
             // (1 / 2 / 3 per CU: 483 / 280 / 215 us), its 2x2 footprint rarely needs the rows given up: 218 -> 190 us
 #ifdef MEMC_MEASURE
-            if (g_cap_sel == 0) MEMC_BL_FWD(3, 3072);
-            else if (g_cap_sel == 2) MEMC_BL_FWD(3, 1984);     // 5 per CU: 198-202 us
+            if (g_cap_sel == 0) launch_bl_fwd_tiled<3, 3072>(k);
+            else if (g_cap_sel == 2) launch_bl_fwd_tiled<3, 1984>(k);  // 5 per CU: 198-202 us
             else
 #endif
-            MEMC_BL_FWD(3, 2496);
+            launch_bl_fwd_tiled<3, 2496>(k);
         } else {
-            MEMC_BL_FWD(0, 3072);
+            launch_bl_fwd_tiled<0, 3072>(k);
         }
-#undef MEMC_BL_FWD
-#undef MEMC_BL_FWD_R
         if (ws < w) {                          // the ragged row's last columns
-            if (channel == 3)
-                hipLaunchKernelGGL(bl_fwd<3>, dim3((unsigned)tail_y * batch), dim3(256), 0, stream, w, h, channel, 1, tail_y,
-                                   (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, input1, input2, output, ws);
-            else
-                hipLaunchKernelGGL(bl_fwd<0>, dim3((unsigned)tail_y * batch), dim3(256), 0, stream, w, h, channel, 1, tail_y,
-                                   (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, input1, input2, output, ws);
+            if (channel == 3) launch_bl_fwd_direct<3>(k, ws);
+            else launch_bl_fwd_direct<0>(k, ws);
         }
         return launch_status();
     }
-    const int tiles_x = (w + kWave - 1) / kWave, tiles_y = (h + 3) / 4;
-    const unsigned nwg = (unsigned)tiles_x * tiles_y * batch;
     MEMC_PATH("bl_fwd:direct");
-    if (channel == 3)
-        hipLaunchKernelGGL(bl_fwd<3>, dim3(nwg), dim3(256), 0, stream, w, h, channel, tiles_x, tiles_y,
-                           (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, input1, input2, output, 0);
-    else
-        hipLaunchKernelGGL(bl_fwd<0>, dim3(nwg), dim3(256), 0, stream, w, h, channel, tiles_x, tiles_y,
-                           (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, input1, input2, output, 0);
+    if (channel == 3) launch_bl_fwd_direct<3>(k);
+    else launch_bl_fwd_direct<0>(k);
     return launch_status();
 }
 
 #ifdef MEMC_MEASURE
 static int g_bl_bwd_direct = 0;                // A/B: the direct (global atomics) kernel for any channel count
+#else
+constexpr int g_bl_bwd_direct = 0;
 #endif
 
-static int launch_bl_bwd(hipStream_t stream, int w, int h, int channel, int batch, int s1b, int s1c, int s1h,
-                         int s2b, int s2c, int s2h, const float *input1, const float *input2,
-                         const float *gradoutput, float *gradinput1, float *gradinput2)
+static int launch_bl_bwd(const BlBwdCall &k)
 {
-    if (w <= 0 || h <= 0 || channel <= 0 || batch <= 0) return 0;
-    const int ws = w & ~3;                                 // (a ragged width: see launch_bl_fwd)
-    const int tail_y = (h + 3) / 4;
-#ifdef MEMC_MEASURE
+    const int w = k.w, h = k.h, channel = k.channel;
+    if (w <= 0 || h <= 0 || channel <= 0 || k.batch <= 0) return 0;
+    const int ws = w & ~3;
     const bool arm_needs_quads = (g_cap_sel == 0 || g_cap_sel == 1) && ws < w;    // (the rounds 1-2 kernel: whole widths only)
-#else
-    constexpr bool arm_needs_quads = false;
-#endif
-    if (channel == 3 && g_cap_sel != 5 && plane_fits_u32(w, h, {s1h}) && ws >= 4 && !arm_needs_quads) {
-        using G = TileGeom<16>;
-        const int ntx = (ws + G::kTW - 1) / G::kTW;
-        [[maybe_unused]] const int nty = (h + G::kTH - 1) / G::kTH;
-        const int sw = g_tile_walk_sw >= 0 ? g_tile_walk_sw : kDefaultStripe;
+    if (channel == 3 && g_cap_sel != 5 && plane_fits_u32(w, h, {k.s1.h}) && ws >= 4 && !arm_needs_quads) {
         MEMC_PATH("bl_bwd:tiled_c3");
-#ifdef MEMC_MEASURE
-#define MEMC_BL_BWD(CAP)                                                                                        \
-        hipLaunchKernelGGL(bl_bwd_tiled_c3<CAP>, dim3(walk_grid(ntx, nty, batch, sw)), dim3(256),                  \
-                           (tile_lds_bytes<16, CAP>()), stream, w, h, ntx, nty, (int64_t)s1b, (int64_t)s1c, s1h,  \
-                           (int64_t)s2b, (int64_t)s2c, s2h, input1, input2, gradoutput, gradinput1, gradinput2, sw)
-#endif
         // Product: the packed-plane kernel.  The fp64-plane kernel of rounds 1-2 stays as a measurement arm (bl_cap 0: its
         // 48 KiB budget; 1: 39 KiB, which LOSES, 522 -> 601 us: the fixed-pitch plane gets 26 rows instead of 32)
-#ifdef MEMC_MEASURE
-        if (g_cap_sel == 1) MEMC_BL_BWD(2496);
-        else if (g_cap_sel == 0) MEMC_BL_BWD(3072);
-        else
-#endif
-#define MEMC_BL_BWD_PK_R(CAP, NT, RAG)                                                                          \
-        do {                                                                                                       \
-            constexpr size_t lds = CAP * 16 + 32 * (NT / kWave);    /* image or planes; 32 bytes per wave: box, bounds */ \
-            allow_big_lds(bl_bwd_c3_pk<CAP, NT, RAG>, lds);    /* per launch: the attribute belongs to the CURRENT device */ \
-            const int ntyk = (h + NT / 16 - 1) / (NT / 16);                                                        \
-            hipLaunchKernelGGL((bl_bwd_c3_pk<CAP, NT, RAG>), dim3(walk_grid(ntx, ntyk, batch, sw)), dim3(NT), lds, \
-                               stream, w, h, ntx, ntyk, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, \
-                               s2h, input1, input2, gradoutput, gradinput1, gradinput2, sw);                       \
-        } while (0)
-#define MEMC_BL_BWD_PK(CAP, NT)                                                                                 \
-        do {                                                                                                       \
-            if (ws < w) MEMC_BL_BWD_PK_R(CAP, NT, true);                                                           \
-            else MEMC_BL_BWD_PK_R(CAP, NT, false);                                                                 \
-        } while (0)
         // 64 x 32 tiles on 512 lanes, 64 KiB, two workgroups per CU.  The flush's global atomics bound this kernel, and a
         // bigger tile's box holds fewer cells per site: against 64 x 16 tiles on 256 lanes (bl_cap 4; 3: the same in
         // 39 KiB) 526 -> 484 us smooth, 759 -> 640 i.i.d., 478 -> 459 video; 64 x 64 tiles on 1024 lanes, one workgroup per CU
         // and nothing to overlap its phases with, lose: 548 / 885 / 512 (profiles/r03_bl_bwd_ab.txt).
 #ifdef MEMC_MEASURE
-        if (g_cap_sel == 3) MEMC_BL_BWD_PK(2496, 256);
-        else if (g_cap_sel == 4) MEMC_BL_BWD_PK(3072, 256);
+        if (g_cap_sel == 1) launch_bl_bwd_tiled_c3<2496>(k);
+        else if (g_cap_sel == 0) launch_bl_bwd_tiled_c3<3072>(k);
+        else if (g_cap_sel == 3) launch_bl_bwd_c3_pk<2496, 256>(k);
+        else if (g_cap_sel == 4) launch_bl_bwd_c3_pk<3072, 256>(k);
         else
 #endif
-        MEMC_BL_BWD_PK(4096, 512);
-#undef MEMC_BL_BWD_PK
-#undef MEMC_BL_BWD_PK_R
-#undef MEMC_BL_BWD
-        if (ws < w)                            // the ragged row's last columns: both kernels ADD into gradinput1
-            hipLaunchKernelGGL(bl_bwd<3>, dim3((unsigned)tail_y * batch), dim3(256), 0, stream, w, h, channel, 1, tail_y,
-                               (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, input1, input2,
-                               gradoutput, gradinput1, gradinput2, ws);
+        launch_bl_bwd_c3_pk<4096, 512>(k);
+        if (ws < w) launch_bl_bwd_direct<3>(k, ws);        // the ragged row's last columns: both kernels ADD into gradinput1
         return launch_status();
     }
 #ifdef MEMC_MEASURE
     g_bwd_cn_allow_c3 = g_cap_sel == 5;                    // arm: RGB through the owner kernels (one chunk, a padded plane)
-    if (channel != 3 || g_cap_sel == 5) {
-#else
-    if (channel != 3) {                                    // many channels: fi_bwd_cn.hip (owner-computes)
 #endif
-#ifdef MEMC_MEASURE
-        const bool direct_only = g_bl_bwd_direct != 0;
-#else
-        constexpr bool direct_only = false;
-#endif
-        const int taken = bl_bwd_cn_launch(stream, w, h, channel, batch, s1b, s1c, s1h, s2b, s2c, s2h, input1, input2,
-                                           gradoutput, gradinput1, gradinput2, direct_only);
+    if (channel != 3 || g_cap_sel == 5) {                  // many channels: fi_bwd_cn.hip (owner-computes)
+        // (the strides came in as the launcher ABI's ints)
+        const int taken = bl_bwd_cn_launch(k.stream, w, h, channel, k.batch, (int)k.s1.b, (int)k.s1.c, k.s1.h, (int)k.s2.b,
+                                           (int)k.s2.c, k.s2.h, k.in1, k.flow, k.gout, k.gin1, k.gin2, g_bl_bwd_direct != 0);
         if (taken != 0) {
             MEMC_PATH("bl_bwd:owner");
             return taken > 0 ? 0 : -1;
         }
     }
-    const int tiles_x = (w + kWave - 1) / kWave, tiles_y = (h + 3) / 4;
-    const unsigned nwg = (unsigned)tiles_x * tiles_y * batch;
     MEMC_PATH("bl_bwd:direct");
-    if (channel == 3)
-        hipLaunchKernelGGL(bl_bwd<3>, dim3(nwg), dim3(256), 0, stream, w, h, channel, tiles_x, tiles_y,
-                           (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, input1, input2,
-                           gradoutput, gradinput1, gradinput2, 0);
-    else
-        hipLaunchKernelGGL(bl_bwd<0>, dim3(nwg), dim3(256), 0, stream, w, h, channel, tiles_x, tiles_y,
-                           (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, input1, input2,
-                           gradoutput, gradinput1, gradinput2, 0);
+    if (channel == 3) launch_bl_bwd_direct<3>(k);
+    else launch_bl_bwd_direct<0>(k);
     return launch_status();
 }
 
@@ -591,7 +575,8 @@ extern "C" int InterpolationLayer_gpu_forward_kernel(
     const float *input1, const float *input2, float *output)
 {
     (void)nElement; (void)s1w; (void)s2w;
-    return launch_bl_fwd((hipStream_t)stream, w, h, channel, batch, s1b, s1c, s1h, s2b, s2c, s2h, input1, input2, output);
+    return launch_bl_fwd({(hipStream_t)stream, w, h, channel, batch, plane(s1b, s1c, s1h), plane(s2b, s2c, s2h), input1,
+                          input2, output});
 }
 
 extern "C" int InterpolationLayer_gpu_backward_kernel(
@@ -601,8 +586,8 @@ extern "C" int InterpolationLayer_gpu_backward_kernel(
     const float *input1, const float *input2, const float *gradoutput, float *gradinput1, float *gradinput2)
 {
     (void)nElement; (void)s1w; (void)s2w;
-    return launch_bl_bwd((hipStream_t)stream, w, h, channel, batch, s1b, s1c, s1h, s2b, s2c, s2h, input1, input2,
-                         gradoutput, gradinput1, gradinput2);
+    return launch_bl_bwd({(hipStream_t)stream, w, h, channel, batch, plane(s1b, s1c, s1h), plane(s2b, s2c, s2h), input1,
+                          input2, gradoutput, gradinput1, gradinput2});
 }
 
 extern "C" int InterpolationChLayer_gpu_forward_kernel(
@@ -612,7 +597,8 @@ extern "C" int InterpolationChLayer_gpu_forward_kernel(
     const float *input1, const float *input2, float *output)
 {
     (void)nElement; (void)s1w; (void)s2w;
-    return launch_bl_fwd((hipStream_t)stream, w, h, channel, batch, s1b, s1c, s1h, s2b, s2c, s2h, input1, input2, output);
+    return launch_bl_fwd({(hipStream_t)stream, w, h, channel, batch, plane(s1b, s1c, s1h), plane(s2b, s2c, s2h), input1,
+                          input2, output});
 }
 
 extern "C" int InterpolationChLayer_gpu_backward_kernel(
@@ -622,6 +608,6 @@ extern "C" int InterpolationChLayer_gpu_backward_kernel(
     const float *input1, const float *input2, const float *gradoutput, float *gradinput1, float *gradinput2)
 {
     (void)nElement; (void)s1w; (void)s2w;
-    return launch_bl_bwd((hipStream_t)stream, w, h, channel, batch, s1b, s1c, s1h, s2b, s2c, s2h, input1, input2,
-                         gradoutput, gradinput1, gradinput2);
+    return launch_bl_bwd({(hipStream_t)stream, w, h, channel, batch, plane(s1b, s1c, s1h), plane(s2b, s2c, s2h), input1,
+                          input2, gradoutput, gradinput1, gradinput2});
 }

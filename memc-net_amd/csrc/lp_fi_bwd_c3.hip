@@ -12,6 +12,7 @@
 #include "memc_common.hpp"
 #include "memc_fi_bwd_c3.hpp"
 #include "memc_desc.hpp"
+#include "memc_launch.hpp"
 #include "memc_warp_lp_grad.h"
 
 #include <math.h>
@@ -47,35 +48,34 @@ using namespace memc;
 constexpr int kErr = -1;
 constexpr int kNotCovered = 1;
 
-inline int64_t S(const memc_tensor4 *t, int i) { return t->stride[i]; }
+template <class P, class FT, class GT, int PART>
+void launch_fi_bwd_c3_lp(const FiBwdCall<st_t<P>, st_t<FT>, st_t<GT>> &k)
+{
+    using G = TileGeom<16>;
+    const int ntx = (k.w + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH;
+    hipLaunchKernelGGL((fi_bwd_c3_lp<P, FT, GT, PART>), dim3((unsigned)ntx * nty * k.batch), dim3(256), PkGeom::kLds, k.stream,
+                       k.w, k.h, ntx, nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h,
+                       k.in1, k.flow, k.filt, k.gout, k.gin1, k.gin2, k.gin3);
+}
 
 template <class P, class FT, class GT>
 int fi_bwd_lp_launch(hipStream_t stream, int w, int h, int n, const memc_tensor4 *in1, const memc_tensor4 *flow,
                      const memc_tensor4 *filt, const memc_tensor4 *gout, const memc_tensor4 *gin1, const memc_tensor4 *gin2,
                      const memc_tensor4 *gin3)
 {
-    using G = TileGeom<16>;
-    const int ntx = (w + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;
-    const dim3 grid((unsigned)ntx * nty * n);
-    const auto *i1 = reinterpret_cast<const st_t<P> *>(in1->data);
-    const auto *fl = reinterpret_cast<const st_t<FT> *>(flow->data);
-    const auto *fk = reinterpret_cast<const st_t<P> *>(filt->data);
-    const auto *go = reinterpret_cast<const st_t<GT> *>(gout->data);
-    auto *g1 = gin1 ? reinterpret_cast<float *>(gin1->data) : nullptr;
-    auto *g2 = reinterpret_cast<st_t<FT> *>(gin2->data);
-    auto *g3 = reinterpret_cast<st_t<P> *>(gin3->data);
-#define MEMC_FI_BWD_LP(PART)                                                                                            \
-    hipLaunchKernelGGL((fi_bwd_c3_lp<P, FT, GT, PART>), grid, dim3(256), PkGeom::kLds, stream, w, h, ntx, nty, n,        \
-                       S(in1, 0), S(in1, 1), (int)S(in1, 2), S(flow, 0), S(flow, 1), (int)S(flow, 2), S(filt, 0),         \
-                       S(filt, 1), (int)S(filt, 2), i1, fl, fk, go, g1, g2, g3)
-    if (g1) {                                  // the whole backward (the fp32 launcher's PART 0)
+    const FiBwdCall<st_t<P>, st_t<FT>, st_t<GT>> k = {
+        stream, w, h, 3, n, 4, plane(in1), plane(flow), plane(filt),
+        reinterpret_cast<const st_t<P> *>(in1->data), reinterpret_cast<const st_t<FT> *>(flow->data),
+        reinterpret_cast<const st_t<P> *>(filt->data), reinterpret_cast<const st_t<GT> *>(gout->data),
+        gin1 ? reinterpret_cast<float *>(gin1->data) : nullptr, reinterpret_cast<st_t<FT> *>(gin2->data),
+        reinterpret_cast<st_t<P> *>(gin3->data)};
+    if (k.gin1) {                              // the whole backward (the fp32 launcher's PART 0)
         t_lp_grad_path = "fi_bwd_lp:tiled_c3";
-        MEMC_FI_BWD_LP(0);
+        launch_fi_bwd_c3_lp<P, FT, GT, 0>(k);
     } else {                                   // no image gradient (its PART 2)
         t_lp_grad_path = "fi_bwd_lp:tiled_c3_noimage";
-        MEMC_FI_BWD_LP(2);
+        launch_fi_bwd_c3_lp<P, FT, GT, 2>(k);
     }
-#undef MEMC_FI_BWD_LP
     return launch_status();
 }
 

@@ -17,6 +17,7 @@
 #include "memc_fi.hpp"
 #include "memc_lp.hpp"
 #include "memc_desc.hpp"
+#include "memc_launch.hpp"
 #include "memc_warp_lp.h"
 
 #include <math.h>
@@ -343,39 +344,39 @@ namespace {
 using namespace memc;
 constexpr int kErr = -1;
 
-inline int64_t S(const memc_tensor4 *t, int i) { return t->stride[i]; }
+template <class T, class FT, bool RGB, bool RAGGED = false>
+void launch_fi_fwd_lp_tiled(const FiFwdCall<st_t<T>, st_t<FT>> &k)
+{
+    using G = TileGeom<16>;
+    const int ntx = (k.w + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH;
+    hipLaunchKernelGGL((fi_fwd_lp_tiled<T, FT, RGB, RAGGED>), dim3((unsigned)ntx * nty * k.batch), dim3(256),
+                       tile_lds_bytes<16>(), k.stream, k.w, k.h, k.channel, ntx, nty, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c,
+                       k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.in1, k.flow, k.filt, k.out);
+}
 
 template <class T, class FT>
 int fi_fwd_lp_launch(hipStream_t stream, int w, int h, int c, int n, int fs, bool tiled, const memc_tensor4 *in1,
                      const memc_tensor4 *flow, const memc_tensor4 *filt, const memc_tensor4 *out)
 {
-    const auto *i1 = reinterpret_cast<const st_t<T> *>(in1->data);
-    const auto *fl = reinterpret_cast<const st_t<FT> *>(flow->data);
-    const auto *fk = reinterpret_cast<const st_t<T> *>(filt->data);
-    auto *o = reinterpret_cast<st_t<T> *>(out->data);
+    const FiFwdCall<st_t<T>, st_t<FT>> k = {
+        stream, w, h, c, n, fs, plane(in1), plane(flow), plane(filt),
+        reinterpret_cast<const st_t<T> *>(in1->data), reinterpret_cast<const st_t<FT> *>(flow->data),
+        reinterpret_cast<const st_t<T> *>(filt->data), reinterpret_cast<st_t<T> *>(out->data)};
     if (tiled) {
-        using G = TileGeom<16>;
-        const int ntx = (w + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;
-        const dim3 grid((unsigned)ntx * nty * n);
-#define MEMC_LP_TILED(RGB, RAGGED)                                                                                      \
-        hipLaunchKernelGGL((fi_fwd_lp_tiled<T, FT, RGB, RAGGED>), grid, dim3(256), tile_lds_bytes<16>(), stream, w, h, c, ntx, nty, \
-                           S(in1, 0), S(in1, 1), (int)S(in1, 2), S(flow, 0), S(flow, 1), (int)S(flow, 2), S(filt, 0),     \
-                           S(filt, 1), (int)S(filt, 2), i1, fl, fk, o)
         if (c == 3) {
             t_lp_path = "fi_fwd_lp:tiled_c3";
-            MEMC_LP_TILED(true, false);
+            launch_fi_fwd_lp_tiled<T, FT, true, false>(k);
         } else {
             t_lp_path = "fi_fwd_lp:tiled_c4n";
-            if (c % 4 == 0) MEMC_LP_TILED(false, false);
-            else MEMC_LP_TILED(false, true);
+            if (c % 4 == 0) launch_fi_fwd_lp_tiled<T, FT, false, false>(k);
+            else launch_fi_fwd_lp_tiled<T, FT, false, true>(k);
         }
-#undef MEMC_LP_TILED
     } else {
         const int tiles_x = (w + kWave - 1) / kWave, tiles_y = (h + 3) / 4;
         t_lp_path = "fi_fwd_lp:direct";
         hipLaunchKernelGGL((fi_fwd_lp_direct<T, FT>), dim3((unsigned)tiles_x * tiles_y * n), dim3(256), 0, stream, w, h, c, fs,
-                           tiles_x, tiles_y, S(in1, 0), S(in1, 1), (int)S(in1, 2), S(flow, 0), S(flow, 1), (int)S(flow, 2),
-                           S(filt, 0), S(filt, 1), (int)S(filt, 2), i1, fl, fk, o);
+                           tiles_x, tiles_y, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.in1,
+                           k.flow, k.filt, k.out);
     }
     return launch_status();
 }
@@ -388,20 +389,20 @@ int fi_blend_lp_launch(hipStream_t stream, int w, int h, int c, int n, int fs, b
     const auto *k0 = reinterpret_cast<const st_t<T> *>(t[4]->data), *k1 = reinterpret_cast<const st_t<T> *>(t[5]->data);
     const auto *q0 = reinterpret_cast<const st_t<T> *>(t[6]->data), *q1 = reinterpret_cast<const st_t<T> *>(t[7]->data);
     auto *o = reinterpret_cast<st_t<T> *>(t[8]->data);
-    const memc_tensor4 *in = t[0], *fl = t[2], *fk = t[4], *oc = t[6];
+    const Plane s1 = plane(t[0]), s2 = plane(t[2]), s3 = plane(t[4]), so = plane(t[6]);      // (so.c is not used)
     if (tiled) {
         using G = TileGeom<16>;
         const int ntx = (w + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;
         t_lp_path = "fi_blend_lp:tiled_c3";
         hipLaunchKernelGGL((fi_blend_lp_tiled<T, FT>), dim3((unsigned)ntx * nty * n), dim3(256), tile_lds_bytes<16>(), stream,
-                           w, h, ntx, nty, S(in, 0), S(in, 1), (int)S(in, 2), S(fl, 0), S(fl, 1), (int)S(fl, 2), S(fk, 0),
-                           S(fk, 1), (int)S(fk, 2), S(oc, 0), (int)S(oc, 2), i0, i2, f0, f1, k0, k1, q0, q1, o);
+                           w, h, ntx, nty, s1.b, s1.c, s1.h, s2.b, s2.c, s2.h, s3.b, s3.c, s3.h, so.b, so.h, i0, i2, f0, f1, k0,
+                           k1, q0, q1, o);
     } else {
         const int tiles_x = (w + kWave - 1) / kWave, tiles_y = (h + 3) / 4;
         t_lp_path = "fi_blend_lp:direct";
         hipLaunchKernelGGL((fi_blend_lp_direct<T, FT>), dim3((unsigned)tiles_x * tiles_y * n), dim3(256), 0, stream, w, h, c,
-                           fs, tiles_x, tiles_y, S(in, 0), S(in, 1), (int)S(in, 2), S(fl, 0), S(fl, 1), (int)S(fl, 2),
-                           S(fk, 0), S(fk, 1), (int)S(fk, 2), S(oc, 0), (int)S(oc, 2), i0, i2, f0, f1, k0, k1, q0, q1, o);
+                           fs, tiles_x, tiles_y, s1.b, s1.c, s1.h, s2.b, s2.c, s2.h, s3.b, s3.c, s3.h, so.b, so.h, i0, i2, f0,
+                           f1, k0, k1, q0, q1, o);
     }
     return launch_status();
 }

@@ -11,6 +11,7 @@
 
 #if defined(__cplusplus) && defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#include "memc_launch.hpp"
 namespace memc {
 // fi_bwd_cn.hip: FilterInterpolation backward for C >= 4 (a ragged last chunk is padded), fs == 4 (tap-gradient kernel +
 // owner-computes image gradient).  1: taken, 0: not taken (the caller falls back to the direct kernel; for this class of channel counts
@@ -25,18 +26,13 @@ bool fi_bwd_cn_class(int channel, int filter_size);
 #ifdef MEMC_MEASURE
 extern bool g_bwd_cn_allow_c3;               // arm (bl_cap 5): the bilinear warp's RGB backward through the owner kernels
 #endif
-// fi_bwd_c3.hip: the same operator for RGB (C == 3), fs == 4, LDS-tiled.  1: taken, 0: geometry not 16-byte aligned
-// (the caller takes the direct kernel), -1: launch error.  variant: measurement arm (-1 in the product).
-int fi_bwd_c3_launch(hipStream_t stream, int w, int h, int batch,
-                     int s1b, int s1c, int s1h, int s2b, int s2c, int s2h, int s3b, int s3c, int s3h,
-                     const float *input1, const float *input2, const float *input3, const float *gradoutput,
-                     float *gradinput1, float *gradinput2, float *gradinput3, int variant);
+// fi_bwd_c3.hip: the same operator for RGB (C == 3), fs == 4, LDS-tiled.  1: taken, 2: taken for the whole quads of a ragged
+// width (the caller runs the direct kernel on the columns behind them), 0: not taken (the caller takes the direct kernel),
+// -1: launch error.  variant: measurement arm (-1 in the product).
+int fi_bwd_c3_launch(const FiBwdCall<> &call, int variant);
 #ifdef MEMC_MEASURE
 // arms/fi_bwd_c3_arms.hip (measurement build only): the kernels of rounds 1-2 and their ablation arms
-int fi_bwd_c3_arm_launch(int variant, hipStream_t stream, int w, int h, int ntx, int nty, int batch,
-                         int s1b, int s1c, int s1h, int s2b, int s2c, int s2h, int s3b, int s3c, int s3h,
-                         const float *input1, const float *input2, const float *input3, const float *gradoutput,
-                         float *gradinput1, float *gradinput2, float *gradinput3);
+int fi_bwd_c3_arm_launch(int variant, const FiBwdCall<> &call);
 int fi_bwd_c3_arms_set_trace_buffer(unsigned long long *device_buffer);
 #endif
 // ... and the bilinear warp's backward (Interpolation / InterpolationCh) for the same class of channel counts

@@ -1,0 +1,60 @@
+// memc_launch.hpp -- how the warp launchers hand a call to a kernel (host code only): the strides of a tensor as the
+// kernels take them, and one call descriptor per operator family, filled once at the top of an entry point.  The launch
+// function of a kernel family -- tile count, grid, LDS bytes and the argument list, spelled once -- is a function template
+// beside the kernel (launch_fi_fwd_tiled_fs4 in filter_interpolation.hip, ...).  The descriptors are templates over the
+// tensors' storage: float in the fp32 library, st_t<...> (memc_lp.hpp) in the half-precision ones.
+#pragma once
+
+#include "memc_warp_lp.h"                      // memc_tensor4
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace memc {
+
+// The three strides a kernel takes per tensor, in elements: batch and channel as int64_t (b * s.b must not wrap), the row
+// stride as int.  The w stride is 1 (memc_desc.hpp: ok()).  THE place where a launcher's strides are widened.
+struct Plane {
+    int64_t b, c;
+    int h;
+};
+inline Plane plane(int sb, int sc, int sh) { return {(int64_t)sb, (int64_t)sc, sh}; }          // the fp32 launcher ABI
+inline Plane plane(const memc_tensor4 *t) { return {t->stride[0], t->stride[1], (int)t->stride[2]}; }
+
+// FilterInterpolation forward.  s1: input1 and output; s2: the flow; s3: the filter taps.
+template <class T = float, class FT = T>
+struct FiFwdCall {
+    hipStream_t stream;
+    int w, h, channel, batch, filter_size;
+    Plane s1, s2, s3;
+    const T *in1;  const FT *flow;  const T *filt;  T *out;
+};
+
+// FilterInterpolation backward.  s1: input1, gradoutput and gradinput1 (always fp32: the tiles' flushes add into it; NULL:
+// not wanted); s2: the flow and gradinput2; s3: the taps and gradinput3.
+template <class T = float, class FT = T, class GT = T>
+struct FiBwdCall {
+    hipStream_t stream;
+    int w, h, channel, batch, filter_size;
+    Plane s1, s2, s3;
+    const T *in1;  const FT *flow;  const T *filt;  const GT *gout;
+    float *gin1;  FT *gin2;  T *gin3;
+};
+
+// The bilinear warp (Interpolation / InterpolationCh).  s1: input1, output / gradoutput, gradinput1; s2: the flow, gradinput2.
+struct BlFwdCall {
+    hipStream_t stream;
+    int w, h, channel, batch;
+    Plane s1, s2;
+    const float *in1, *flow;
+    float *out;
+};
+struct BlBwdCall {
+    hipStream_t stream;
+    int w, h, channel, batch;
+    Plane s1, s2;
+    const float *in1, *flow, *gout;
+    float *gin1, *gin2;
+};
+
+}  // namespace memc
