@@ -4,8 +4,11 @@
         + occlusion1 * FilterInterpolation(input2, flow1, filter1)
 
 i.e. `FilterInterpolate` of networks/MEMC_Net_star.py:264-277 as ONE kernel (the two warped frames are never
-written).  Differentiable: the backward pass goes through the reference-API entry points (two forward
-recomputations + two backward launches; nothing but the inputs is kept for it).
+written).  Differentiable; nothing but the inputs is kept for the backward pass.  float32: a direction whose image
+does not need a gradient (the frames of the networks are data) is ONE kernel of libmemc_hip_blend_grad.so
+(include/memc_warp_blend_grad.h) on the raw gradoutput: flow, tap and occlusion gradients in one pass, image gradient None.
+A direction whose image does need one, or a shape that kernel does not cover, is composed from the reference-API entry
+points (a forward recomputation + a backward launch), as every direction was before that kernel existed.
 
 The fused kernel covers what the networks use (RGB, 4x4 filters, widths a multiple of 4); any other shape is
 composed from FilterInterpolationLayer calls -- same values, no error.
@@ -24,6 +27,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 import my_package._ext.my_lib as my_lib
+import my_package._ext.my_lib_blend_grad as my_lib_blend_grad
 import my_package._ext.my_lib_lp as my_lib_lp
 from ._common import cast, check, f32c, flow_dtype, payload_dtype, require_gpu
 from .FilterInterpolationLayer import FilterInterpolationLayer, backward_lp, lp_backward_covered
@@ -47,28 +51,58 @@ def _warp(x, flow, filt):
     return out
 
 
-def _blend_backward(saved, gradoutput, half=None):
-    """gradients of occ0 * FI(in0, flow0, filt0) + occ1 * FI(in2, flow1, filt1) w.r.t. its eight inputs, through the
-    reference-API entry points (two forward recomputations + two backward launches).  half: the float16 / bfloat16
-    tensors that `saved` widens -- each direction's backward launch then runs on them (libmemc_hip_lp_grad.so) where the
-    library covers it; its flow / tap gradients come back in their dtypes, the image gradient in float32."""
+def _direction_backward(x, flow, filt, occ, gradoutput, half=None):
+    """(image, flow, tap, occlusion) gradients of ONE direction occ * FI(x, flow, filt) of the blend, composed from the
+    reference-API entry points: a forward recomputation, two elementwise passes, a zero-filled image gradient and the
+    warp's whole backward.  half: the direction's float16 / bfloat16 (x, flow, filt) that the float32 arguments widen --
+    the backward launch then runs on them (libmemc_hip_lp_grad.so) where the library covers it; its flow / tap
+    gradients come back in their dtypes, the image gradient in float32."""
+    warped = _warp(x, flow, filt)                            # recomputed, not stored by the forward pass
+    g_occ = (gradoutput * warped).sum(dim=1, keepdim=True)
+    g_warp = (gradoutput * occ).contiguous()
+    g_x = torch.zeros_like(x)
+    g_lp = None
+    if half is not None and lp_backward_covered(half[0], half[2]):
+        g_lp = backward_lp(half[0], half[1], half[2], g_warp, g_x)
+    if g_lp is not None:
+        g_flow, g_filt = g_lp
+    else:
+        g_flow, g_filt = torch.empty_like(flow), torch.empty_like(filt)
+        check(my_lib.FilterInterpolationLayer_gpu_backward(x, flow, filt, g_warp, g_x, g_flow, g_filt),
+              "FilterInterpolationLayer_gpu_backward")
+    return g_x, g_flow, g_filt, g_occ
+
+
+def _direction_backward_fused(x, flow, filt, occ, gradoutput):
+    """(flow, tap, occlusion) gradients of ONE direction of the blend whose image wants no gradient, from ONE kernel of
+    libmemc_hip_blend_grad.so on the raw gradoutput (float32; every element of the three is assigned), or None where that
+    kernel does not cover the call (anything but RGB, 16 taps and a width that is a multiple of four from 8 on)."""
+    g_flow, g_filt, g_occ = torch.empty_like(flow), torch.empty_like(filt), torch.empty_like(occ)
+    status = my_lib_blend_grad.FilterInterpolationBlendLayer_gpu_backward(x, flow, filt, occ, gradoutput, g_flow, g_filt,
+                                                                          g_occ)
+    if status == 1:
+        return None
+    check(status, "FilterInterpolationBlendLayer_gpu_backward")
+    return g_flow, g_filt, g_occ
+
+
+def _blend_backward(saved, gradoutput, half=None, needs_image_grad=(True, True)):
+    """gradients of occ0 * FI(in0, flow0, filt0) + occ1 * FI(in2, flow1, filt1) w.r.t. its eight inputs.  A direction
+    whose image needs a gradient (needs_image_grad[d]), and every direction of a half call, is composed from the
+    reference-API entry points (_direction_backward: a forward recomputation + a backward launch).  A float32 direction
+    whose image needs none takes the fused kernel (_direction_backward_fused) where it covers the call: its image gradient
+    is None.  half: the float16 / bfloat16 tensors that `saved` widens."""
     input0, input2, flow0, flow1, filter0, filter1, occ0, occ1 = saved
     grads = []
     for d, (x, flow, filt, occ) in enumerate(((input0, flow0, filter0, occ0), (input2, flow1, filter1, occ1))):
-        warped = _warp(x, flow, filt)                        # recomputed, not stored by the forward pass
-        g_occ = (gradoutput * warped).sum(dim=1, keepdim=True)
-        g_warp = (gradoutput * occ).contiguous()
-        g_x = torch.zeros_like(x)
-        g_lp = None
-        if half is not None and lp_backward_covered(half[d], half[4 + d]):
-            g_lp = backward_lp(half[d], half[2 + d], half[4 + d], g_warp, g_x)
-        if g_lp is not None:
-            g_flow, g_filt = g_lp
+        fused = None
+        if half is None and not needs_image_grad[d]:
+            fused = _direction_backward_fused(x, flow, filt, occ, gradoutput)
+        if fused is not None:
+            grads.append((None,) + fused)
         else:
-            g_flow, g_filt = torch.empty_like(flow), torch.empty_like(filt)
-            check(my_lib.FilterInterpolationLayer_gpu_backward(x, flow, filt, g_warp, g_x, g_flow, g_filt),
-                  "FilterInterpolationLayer_gpu_backward")
-        grads.append((g_x, g_flow, g_filt, g_occ))
+            grads.append(_direction_backward(x, flow, filt, occ, gradoutput,
+                                             None if half is None else (half[d], half[2 + d], half[4 + d])))
     (gx0, gf0, gk0, go0), (gx2, gf1, gk1, go1) = grads
     return gx0, gx2, gf0, gf1, gk0, gk1, go0, go1
 
@@ -88,7 +122,7 @@ class _FilterInterpolationBlendFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gradoutput):
-        return _blend_backward(ctx.saved_tensors, f32c(gradoutput))
+        return _blend_backward(ctx.saved_tensors, f32c(gradoutput), needs_image_grad=ctx.needs_input_grad[:2])
 
 
 class _FilterInterpolationBlendLpFunction(Function):

@@ -153,6 +153,41 @@ def bench_fi_blend(rows, dev, B, H, W, flow_kind):
     report(rows, "fi_blend composed (2 fwd + torch blend) %dx%dx%d" % (B, H, W), B * H * W, 188, med, mn)
 
 
+def bench_fi_blend_bwd(rows, dev, B, H, W, flow_kind, windows=6):
+    """ONE direction of the blend's backward for an image that wants no gradient, as the layer runs it (allocations
+    included): the fused kernel of libmemc_hip_blend_grad.so (176 B/site: image 12 + flow 8 + taps 64 + gradoutput 12 +
+    occlusion 4 read, 8 + 64 + 4 written) against the composition it replaces (a forward warp, two elementwise passes, a
+    zero fill and the warp's whole backward).  Same process, alternating windows; the rows carry each window's median
+    and the window-to-window spread (largest - smallest window median)."""
+    from my_package.functions import FilterInterpolationBlendLayer as BL
+    a = synth.torch_inputs(dev, B, 3, H, W, flow_kind=flow_kind, seed=21, with_grad=True)
+    occ = torch.rand(B, 1, H, W, device=dev)
+    gout = a["gout"] - 0.5
+    routes = {"fused": lambda: BL._direction_backward_fused(a["x"], a["flow"], a["filt"], occ, gout),
+              "composed": lambda: BL._direction_backward(a["x"], a["flow"], a["filt"], occ, gout)}
+    assert routes["fused"]() is not None, "the fused kernel declined %dx3x%dx%d" % (B, H, W)
+    burst = 10 if B * H * W < 4e6 else 1                  # small launches: see time_launches
+    for fn in routes.values():                            # pre-warm: allocator and clocks
+        for _ in range(10):
+            fn()
+    torch.cuda.synchronize()
+    per_window = {k: [] for k in routes}
+    samples = {k: [] for k in routes}
+    for _ in range(windows):
+        for k, fn in routes.items():
+            med, _mn = time_launches(fn, warmup=2, iters=8, burst=burst)
+            per_window[k].append(med)
+            samples[k].append(med)
+    for k in routes:
+        med = statistics.median(samples[k])
+        report(rows, "fi_blend_bwd %-8s one direction, no image gradient %dx%dx%d flow=%s" % (k, B, H, W, flow_kind),
+               B * H * W, 176, med, min(per_window[k]),
+               {"window_medians_us": [round(t * 1e6, 1) for t in per_window[k]],
+                "window_spread_us": round((max(per_window[k]) - min(per_window[k])) * 1e6, 1)})
+        print("    windows (us): %s   spread %.1f us" % (" ".join("%.1f" % (t * 1e6) for t in per_window[k]),
+                                                          (max(per_window[k]) - min(per_window[k])) * 1e6), flush=True)
+
+
 def bench_fi_ctx(rows, dev, B, C, H, W, flow_kind):
     """the warp stage of MEMC_Net_star for one frame pair (blended frame + both warped context tensors): one launch
     per direction with shared flow / tap reads (section 8f-3) against the fused blend + two context warps"""
@@ -354,6 +389,10 @@ def main():
             bench_fi_fwd(rows, dev, 8, 3, 2160, 3840, "smooth", variants[:1], "c5_4k")
     if want("fi_blend"):
         bench_fi_blend(rows, dev, 32, 720, 1280, "smooth")
+    if want("fi_blend_bwd"):
+        bench_fi_blend_bwd(rows, dev, 8, 256, 448, "smooth")
+        if not args.quick:
+            bench_fi_blend_bwd(rows, dev, 32, 720, 1280, "smooth")
     if want("prologue"):
         bench_prologue(rows, dev, 32, 180, 320)
     if want("fi_ctx"):

@@ -31,15 +31,16 @@ _RES = (("vgpr", r"; NumVgprs: (\d+)"), ("sgpr", r"; TotalNumSgprs: (\d+)"), ("l
 def make_vars(tree):
     """ARCH, CXXFLAGS and the source lists, read from the tree's own Makefile"""
     text = open(os.path.join(tree, CSRC, "Makefile")).read()
-    get = lambda name: re.search(r"^%s\s*[?:]?=\s*(.*)$" % name, text, re.M).group(1).split()
-    return {n: get(n) for n in ("ARCH", "CXXFLAGS", "SRCS", "ARMS", "SRCS_LP", "SRCS_LPG")}
+    find = lambda name: re.search(r"^%s\s*[?:]?=\s*(.*)$" % name, text, re.M)
+    get = lambda name: find(name).group(1).split() if find(name) else []       # (a list an older Makefile lacks: empty)
+    return {n: get(n) for n in ("ARCH", "CXXFLAGS", "SRCS", "ARMS", "SRCS_LP", "SRCS_LPG", "SRCS_BG")}
 
 
 def units(tree):
-    """(label, source, defines): what the four libraries are built from, host-only files left out"""
+    """(label, source, defines): what the libraries are built from, host-only files left out"""
     v = make_vars(tree)
     hip = [s for s in v["SRCS"] if s.endswith(".hip")]
-    return ([("product/" + s, s, []) for s in hip + v["SRCS_LP"] + v["SRCS_LPG"]] +
+    return ([("product/" + s, s, []) for s in hip + v["SRCS_LP"] + v["SRCS_LPG"] + v["SRCS_BG"]] +
             [("measure/" + s, s, ["-DMEMC_MEASURE"]) for s in hip + v["ARMS"]])
 
 
