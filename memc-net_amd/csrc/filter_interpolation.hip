@@ -44,7 +44,7 @@ __device__ __noinline__ void fi_site_scalar(int x, int y, int W, int H, int nch,
                                             const float *plane0, int64_t s1c, int s1h,
                                             const float *flow_p, int64_t s2c, const float *tap_p, int64_t s3c,
                                             float *out_p)
-MEMC_FI_SITE_SCALAR_BODY(F32, F32, int)
+MEMC_FI_SITE_SCALAR_BODY(F32, F32, int, F32)
 #undef MEMC_FI_SITE_SCALAR_BODY
 
 // one chunk of NCH (1..4) channels: stage -> gather -> store.  Everything indexed by channel or site is

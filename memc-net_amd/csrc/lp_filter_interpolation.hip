@@ -12,10 +12,13 @@
 //   fi_fwd_lp_direct / fi_blend_lp_direct   one lane per site, any filter size, any width, any alignment.
 // The LDS holds fp32 pixel quads (staging widens), so the gather and its arithmetic are the fp32 kernels' own: the site
 // geometry, the gather and the one-site paths from global memory are memc_fi.hpp's, the descriptor checks memc_desc.hpp's.
+// The two tiled kernels' bodies (lp_fi_fwd_body.inc, lp_fi_blend_body.inc) are shared with libmemc_hip_mx.so (an fp32
+// image beside half taps).
 #include "memc_common.hpp"
 #include "memc_tile.hpp"
 #include "memc_fi.hpp"
 #include "memc_lp.hpp"
+#include "memc_lp_fi.hpp"
 #include "memc_desc.hpp"
 #include "memc_launch.hpp"
 #include "memc_warp_lp.h"
@@ -26,24 +29,8 @@ namespace memc {
 
 thread_local const char *t_lp_path = "";
 
-// MEMC_FI_SITES and MEMC_FI_LAUNDER (memc_fi.hpp) as functions, for fi_blend_lp_tiled alone: expanded in place, as in
-// every other kernel, its fp16 instantiation is 2 % slower (profiles/r08_refactor_lowp_ab.txt).
-__device__ __forceinline__ FiSite4 fi_sites_fn(int x, int y, int W, int H, bool inb, const f32x4 &fx4, const f32x4 &fy4,
-                                               int &cmin_, int &cmax_, int &rmin_, int &rmax_)
-{
-    MEMC_FI_SITES(g, x, y, W, H, inb, fx4, fy4);
-    cmin_ = cmin; cmax_ = cmax; rmin_ = rmin; rmax_ = rmax;
-    return g;
-}
-__device__ __forceinline__ void fi_launder_fn(f32x4 (&tp)[16], FiSite4 &g) { MEMC_FI_LAUNDER(tp, g); }
-
-// --------------------------------------------------------------------------------------------------
-// Forward, fs == 4, LDS-tiled: 64 x 16 tiles of 256 lanes, one lane = four consecutive sites of a row, strip walk.
-// RGB: one chunk of three channels, bands outside (fi_fwd_tiled_fs4<16, 3, 2, 0>).  Otherwise: bands outside, chunks of
-// four channels inside, the next chunk's staging loads issued before this chunk's gathers (fi_fwd_tiled_c4n<0, 256,
-// RAGGED>).  RAGGED (a channel count that is not a multiple of four, a separate instantiation): the last chunk re-reads the
-// last plane and stores only the channels it has; one workgroup per CU (at two, the bf16 instantiation spills).
-// --------------------------------------------------------------------------------------------------
+// The tiled kernels: the bodies lp_fi_fwd_body.inc / lp_fi_blend_body.inc with the image in T (libmemc_hip_mx.so runs the
+// same bodies on an fp32 image).
 template <class T, class FT, bool RGB, bool RAGGED = false>
 __global__ __launch_bounds__(256, RAGGED ? 1 : 2) void fi_fwd_lp_tiled(
     int W, int H, int C, int tiles_x, int tiles_y,
@@ -51,137 +38,10 @@ __global__ __launch_bounds__(256, RAGGED ? 1 : 2) void fi_fwd_lp_tiled(
     const st_t<T> *__restrict__ in1, const st_t<FT> *__restrict__ flow, const st_t<T> *__restrict__ filt,
     st_t<T> *__restrict__ out)
 {
-    constexpr int LX = 16;
-    using G = TileGeom<LX>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    f32x4 *tile = reinterpret_cast<f32x4 *>(smem);
-    int *bb = reinterpret_cast<int *>(smem + G::kCapPx * 16);
-
-    const TileCoord tc = strip_walk(blockIdx.x, gridDim.x, tiles_x, tiles_y, gridDim.x / (tiles_x * tiles_y));
-    const int b = tc.b, tile_x0 = tc.tx * G::kTW, tile_y0 = tc.ty * G::kTH;
-    const int x = tile_x0 + 4 * (threadIdx.x % LX), y = tile_y0 + threadIdx.x / LX;
-    const bool inb = x < W && y < H;                       // W % 4 == 0: a lane's four sites are in or out together
-    // streams first, unconditional (a clamped in-range address for lanes past the edge; see fi_fwd_tiled_fs4)
-    const int xs = min(x, W - 4), ys = min(y, H - 1);
-    const st_t<FT> *flow_p = flow + b * s2b + (int64_t)ys * s2h + xs;
-    const st_t<T> *tap_p = filt + b * s3b + (int64_t)ys * s3h + xs;
-    const f32x4 fx4 = ld4_stream<FT>(flow_p), fy4 = ld4_stream<FT>(flow_p + s2c);
-    f32x4 tp[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) tp[k] = ld4_stream<T>(tap_p + k * s3c);
-
-    MEMC_FI_SITES(g, x, y, W, H, inb, fx4, fy4);
-    const BBox box = tile_bbox<LX>(cmin, cmax, rmin, rmax, bb);
-    const Bands bands = make_bands<LX>(box);
-    const st_t<T> *in_b = in1 + b * s1b;
-    st_t<T> *out_p = out + b * s1b + (int64_t)y * s1h + x;
-    unsigned done = 0;
-
-    if (RGB) {
-        f32x4 res[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) res[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int bi = 0; bi < bands.n; bi++) {
-            const Region rb = band_region(box, bands, bi);
-            const unsigned sel = inb ? fi_covered(rb, g, W, H) & ~done : 0u;
-            if (bi > 0 && !__syncthreads_or(sel != 0)) continue;
-            done |= sel;
-            const StageSlot sl = stage_slots(rb);
-            const unsigned short *plane[3] = {in_b, in_b + s1c, in_b + 2 * s1c};
-            LpStageRegs<3> sr;
-            lp_stage_load<3>(rb, sl, plane, s1h, sr);
-            lp_stage_store<T, 3>(rb, sl, sr, tile);
-            __syncthreads();
-            MEMC_FI_LAUNDER(tp, g);
-            fi_gather<LX, 3>(rb, g, tp, sel, W, H, tile, res);
-        }
-        if (inb) {
-            if (g.valid != 0xFu) {                         // out-of-range sites copy the input pixel
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const f32x4 own = ld4_cached<T>(in_b + c * s1c + (int64_t)y * s1h + x);
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        if (!((g.valid >> j) & 1)) res[j][c] = own[j];
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 3; c++) st4_stream<T>(out_p + c * s1c, f32x4{res[0][c], res[1][c], res[2][c], res[3][c]});
-        }
-    } else {
-#pragma unroll 1
-        for (int bi = 0; bi < bands.n; bi++) {
-            const Region r = band_region(box, bands, bi);
-            const unsigned sel = inb ? fi_covered(r, g, W, H) & ~done : 0u;
-            // later bands only run when somebody still needs them; the vote is also the barrier that frees the LDS
-            if (bi > 0 && !__syncthreads_or(sel != 0)) continue;
-            done |= sel;
-            // band 0 also writes the out-of-range sites (they copy the input pixel)
-            const unsigned wr = sel | (bi == 0 && inb ? ~g.valid & 0xFu : 0u);
-            const StageSlot sl = stage_slots(r);
-            LpStageRegs<4> sr;
-            auto stage_load = [&](int cb) {                // planes past the last one: the last one again
-                const unsigned short *plane[4];
-#pragma unroll
-                for (int c = 0; c < 4; c++) plane[c] = in_b + (RAGGED ? min(cb + c, C - 1) : cb + c) * s1c;
-                lp_stage_load<4>(r, sl, plane, s1h, sr);
-            };
-            stage_load(0);
-#pragma unroll 1
-            for (int c0 = 0; c0 < C; c0 += 4) {
-                lp_stage_store<T, 4>(r, sl, sr, tile);
-                __syncthreads();
-                // next chunk's rows: in flight while this chunk is gathered (the last iteration re-reads its own chunk)
-                stage_load(c0 + 4 < C ? c0 + 4 : c0);
-                MEMC_FI_LAUNDER(tp, g);
-                f32x4 res[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) res[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                fi_gather<LX, 4>(r, g, tp, sel, W, H, tile, res);
-                const st_t<T> *plane0 = in_b + c0 * s1c;
-                st_t<T> *o = out_p + c0 * s1c;
-                if (wr & ~g.valid) {                       // out-of-range sites copy the input pixel
-#pragma unroll
-                    for (int c = 0; c < 4; c++) {
-                        if (RAGGED && c0 + c >= C) continue;
-                        const f32x4 own = ld4_cached<T>(plane0 + c * s1c + (int64_t)y * s1h + x);
-#pragma unroll
-                        for (int j = 0; j < 4; j++)
-                            if (!((g.valid >> j) & 1)) res[j][c] = own[j];
-                    }
-                }
-                if (wr == 0xFu) {
-#pragma unroll
-                    for (int c = 0; c < 4; c++)
-                        if (!RAGGED || c0 + c < C) st4_stream<T>(o + c * s1c, f32x4{res[0][c], res[1][c], res[2][c], res[3][c]});
-                } else if (wr) {                           // a lane whose sites are split over bands
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        if ((wr >> j) & 1) {
-#pragma unroll
-                            for (int c = 0; c < 4; c++)
-                                if (!RAGGED || c0 + c < C) o[c * s1c + j] = narrow<T>(res[j][c]);
-                        }
-                }
-                __syncthreads();
-            }
-        }
-    }
-    unsigned slow = inb ? g.valid & ~done : 0u;            // rare: not coverable within kMaxBands bands
-    while (slow) {
-        const int j = __ffs(slow) - 1;
-        slow &= slow - 1;
-        fi_site_scalar_lp<T, FT>(x + j, y, W, H, C, 4, in_b, s1c, s1h, flow_p + j, s2c, tap_p + j, s3c, out_p + j);
-    }
+    using I = T;                               // the image and the output in the taps' storage
+#include "lp_fi_fwd_body.inc"
 }
 
-// --------------------------------------------------------------------------------------------------
-// Fused dual warp + occlusion blend, RGB, fs == 4 (fi_fwd_blend_c3):
-//     out = occ0 * FI(in0, flow0, filt0) + occ1 * FI(in2, flow1, filt1)       (two products, one sum, rounded once)
-// Both directions' streams are requested up front -- direction 1's taps stay packed (two registers per quad) until
-// direction 0 is done -- then each direction runs its own box -> (bands of) stage -> gather round on the same LDS bytes.
-// --------------------------------------------------------------------------------------------------
 template <class T, class FT>
 __global__ __launch_bounds__(256, 2) void fi_blend_lp_tiled(
     int W, int H, int tiles_x, int tiles_y,
@@ -191,100 +51,8 @@ __global__ __launch_bounds__(256, 2) void fi_blend_lp_tiled(
     const st_t<FT> *__restrict__ flow1, const st_t<T> *__restrict__ filt0, const st_t<T> *__restrict__ filt1,
     const st_t<T> *__restrict__ occ0, const st_t<T> *__restrict__ occ1, st_t<T> *__restrict__ out)
 {
-    constexpr int LX = 16;
-    using G = TileGeom<LX>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    f32x4 *tile = reinterpret_cast<f32x4 *>(smem);
-    int *bb = reinterpret_cast<int *>(smem + G::kCapPx * 16);
-
-    const TileCoord tc = strip_walk(blockIdx.x, gridDim.x, tiles_x, tiles_y, gridDim.x / (tiles_x * tiles_y));
-    const int b = tc.b;
-    const int x = tc.tx * G::kTW + 4 * (int)(threadIdx.x % LX), y = tc.ty * G::kTH + (int)(threadIdx.x / LX);
-    const bool inb = x < W && y < H;
-    const int xs = min(x, W - 4), ys = min(y, H - 1);
-    const int64_t o2 = (int64_t)ys * s2h + xs, o3 = (int64_t)ys * s3h + xs, oo = (int64_t)ys * soh + xs;
-    // all streams of both directions first
-    f32x4 fx[2], fy[2], oc[2], tp[16];
-    u16x4 tq1[16];
-    fx[0] = ld4_stream<FT>(flow0 + b * s2b + o2);  fy[0] = ld4_stream<FT>(flow0 + b * s2b + s2c + o2);
-    fx[1] = ld4_stream<FT>(flow1 + b * s2b + o2);  fy[1] = ld4_stream<FT>(flow1 + b * s2b + s2c + o2);
-#pragma unroll
-    for (int k = 0; k < 16; k++) tp[k] = ld4_stream<T>(filt0 + b * s3b + k * s3c + o3);
-#pragma unroll
-    for (int k = 0; k < 16; k++) tq1[k] = __builtin_nontemporal_load(reinterpret_cast<const u16x4a *>(filt1 + b * s3b + k * s3c + o3));
-    oc[0] = ld4_stream<T>(occ0 + b * sob + oo);
-    oc[1] = ld4_stream<T>(occ1 + b * sob + oo);
-
-    // one direction: box -> (bands of) stage -> gather; returns the warped RGB of the lane's four sites
-    auto warp = [&](const st_t<T> *in_b, const st_t<FT> *flow_b, const st_t<T> *filt_b, const f32x4 &fx4, const f32x4 &fy4,
-                    f32x4 (&res)[4]) {
-        int cmin, cmax, rmin, rmax;
-        FiSite4 g = fi_sites_fn(x, y, W, H, inb, fx4, fy4, cmin, cmax, rmin, rmax);
-        const BBox box = tile_bbox<LX>(cmin, cmax, rmin, rmax, bb);
-        const Bands bands = make_bands<LX>(box);
-#pragma unroll
-        for (int j = 0; j < 4; j++) res[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        unsigned done = 0;
-#pragma unroll 1
-        for (int bi = 0; bi < bands.n; bi++) {
-            const Region rb = band_region(box, bands, bi);
-            const unsigned sel = inb ? fi_covered(rb, g, W, H) & ~done : 0u;
-            if (bi > 0 && !__syncthreads_or(sel != 0)) continue;
-            done |= sel;
-            const StageSlot sl = stage_slots(rb);
-            const unsigned short *plane[3] = {in_b, in_b + s1c, in_b + 2 * s1c};
-            LpStageRegs<3> sr;
-            lp_stage_load<3>(rb, sl, plane, s1h, sr);
-            lp_stage_store<T, 3>(rb, sl, sr, tile);
-            __syncthreads();
-            fi_launder_fn(tp, g);
-            fi_gather<LX, 3>(rb, g, tp, sel, W, H, tile, res);
-        }
-        if (!inb) return;
-        unsigned slow = g.valid & ~done;                   // rare: not coverable within kMaxBands bands
-        while (slow) {
-            const int j = __ffs(slow) - 1;
-            slow &= slow - 1;
-            const st_t<FT> *fp = flow_b + (int64_t)y * s2h + x + j;
-            const FiSite s = fi_locate(x + j, y, W, H, widen<FT>(fp[0]), widen<FT>(fp[s2c]));
-            const int L = s.ix - 1, Tp = s.iy - 1;               // the site's 4 x 4 window
-            f32x4 v;
-#pragma unroll 1
-            for (int c = 0; c < 3; c++)
-                v[c] = fi_site_chan<T, int64_t>(s, 4, L, Tp, L + 4, Tp + 4, W, H, in_b + c * s1c, s1h, filt_b + (int64_t)y * s3h + x + j, s3c);
-            v[3] = 0.f;
-#pragma unroll
-            for (int jj = 0; jj < 4; jj++) res[jj] = jj == j ? v : res[jj];
-        }
-        if (g.valid != 0xFu) {                             // out-of-range sites copy the input pixel
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const f32x4 own = ld4_cached<T>(in_b + c * s1c + (int64_t)y * s1h + x);
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (!((g.valid >> j) & 1)) res[j][c] = own[j];
-            }
-        }
-    };
-
-    f32x4 w0[4], w2[4];
-    warp(in0 + b * s1b, flow0 + b * s2b, filt0 + b * s3b, fx[0], fy[0], w0);
-    __syncthreads();                                       // direction 0's gathers are done: the LDS is free again
-#pragma unroll
-    for (int k = 0; k < 16; k++) tp[k] = widen4<T>(tq1[k]);
-    warp(in2 + b * s1b, flow1 + b * s2b, filt1 + b * s3b, fx[1], fy[1], w2);
-    if (!inb) return;
-    st_t<T> *o = out + b * s1b + (int64_t)y * s1h + x;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        f32x4 v;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const float p0 = oc[0][j] * w0[j][c], p2 = oc[1][j] * w2[j][c];     // two products, one sum (fi_fwd_blend_c3)
-            v[j] = p0 + p2;
-        }
-        st4_stream<T>(o + c * s1c, v);
-    }
+    using I = T;
+#include "lp_fi_blend_body.inc"
 }
 
 // --------------------------------------------------------------------------------------------------

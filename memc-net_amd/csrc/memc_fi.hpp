@@ -102,16 +102,16 @@ __device__ __forceinline__ void fi_gather(const Region &r, const FiSite4 &g, con
 // the reference's order.  P: the storage of the image and the taps (memc_lp.hpp: F32, or F16 / BF16 widened exactly at
 // the load).  I: the type of a row offset -- int where the C ABI hands the kernels `int` strides or the launcher has
 // checked the plane (every fp32 kernel, the half backward); int64_t in the half forward, whose one-lane-per-site kernel
-// takes any plane.
-template <class P = F32, class I = int>
-__device__ __forceinline__ float fi_quad_sum(const st_t<P> *p, int s1h, int W, int H, const st_t<P> *tap_p,
+// takes any plane.  TP: the storage of the taps where it is not the image's (the mixed forward: an fp32 image, half taps).
+template <class P = F32, class I = int, class TP = P>
+__device__ __forceinline__ float fi_quad_sum(const st_t<P> *p, int s1h, int W, int H, const st_t<TP> *tap_p,
                                              int64_t s3c, int fs, int L, int T, int j0, int j1, int i0, int i1)
 {
     float acc = 0.0f;
     for (int j = j0; j <= j1; j++) {
         const I jj = (I)clampi(j, H - 1) * s1h;
         for (int i = i0; i <= i1; i++)
-            acc += widen_f32<P>(p[jj + clampi(i, W - 1)]) * widen_f32<P>(tap_p[((j - T) * fs + (i - L)) * s3c]);
+            acc += widen_f32<P>(p[jj + clampi(i, W - 1)]) * widen_f32<TP>(tap_p[((j - T) * fs + (i - L)) * s3c]);
     }
     return acc;
 }
@@ -120,30 +120,31 @@ __device__ __forceinline__ float fi_quad_sum(const st_t<P> *p, int s1h, int W, i
 // [L, R) and rows [T, Bm) with L = ix + 1 - fs / 2, T = iy + 1 - fs / 2, then the four-term blend.  The window is the
 // caller's, computed once for all channels and handed over as four ints: as a struct, or computed in here, the fp32
 // callers compile to other machine code.
-template <class P = F32, class I = int>
+template <class P = F32, class I = int, class TP = P>
 __device__ __forceinline__ float fi_site_chan(const FiSite &s, int fs, int L, int T, int R, int Bm, int W, int H,
-                                              const st_t<P> *p, int s1h, const st_t<P> *tap_p, int64_t s3c)
+                                              const st_t<P> *p, int s1h, const st_t<TP> *tap_p, int64_t s3c)
 {
-    const float TL = fi_quad_sum<P, I>(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, L, s.ix);
-    const float TR = fi_quad_sum<P, I>(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, s.ix + 1, R - 1);
-    const float BL = fi_quad_sum<P, I>(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, L, s.ix);
-    const float BR = fi_quad_sum<P, I>(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, s.ix + 1, R - 1);
+    const float TL = fi_quad_sum<P, I, TP>(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, L, s.ix);
+    const float TR = fi_quad_sum<P, I, TP>(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, s.ix + 1, R - 1);
+    const float BL = fi_quad_sum<P, I, TP>(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, L, s.ix);
+    const float BR = fi_quad_sum<P, I, TP>(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, s.ix + 1, R - 1);
     return (1 - s.a) * (1 - s.b) * TL + s.a * (1 - s.b) * TR + (1 - s.a) * s.b * BL + s.a * s.b * BR;
 }
 
 // ONE site of the forward for channels [0, nch) of `plane0`, everything read from global memory (flow, taps, image): the
 // rare path for sites whose source window no staged LDS band covers, and the body of the half library's one-lane-per-site
 // kernel.  Same arithmetic order as the fast path; an out-of-range site copies the input pixel.  FT: the storage of the
-// flow.  A macro body, expanded in fi_site_scalar (filter_interpolation.hip: the fp32 library's named function) and in
-// fi_site_scalar_lp below: behind a forwarding call the fp32 function compiles to other machine code.
-#define MEMC_FI_SITE_SCALAR_BODY(P, FT, I)                                                                            \
+// flow; TP: that of the taps.  A macro body, expanded in fi_site_scalar (filter_interpolation.hip: the fp32 library's
+// named function) and in fi_site_scalar_lp / fi_site_scalar_mx below: behind a forwarding call the fp32 function compiles
+// to other machine code.
+#define MEMC_FI_SITE_SCALAR_BODY(P, FT, I, TP)                                                                        \
     {                                                                                                                 \
         const float fx = widen<FT>(flow_p[0]), fy = widen<FT>(flow_p[s2c]);                                           \
         const FiSite s = fi_locate(x, y, W, H, fx, fy);                                                               \
         if (s.valid) {                                                                                                \
             const int L = s.ix + 1 - fs / 2, T = s.iy + 1 - fs / 2, R = L + fs, Bm = T + fs;                          \
             for (int c = 0; c < nch; c++)                                                                             \
-                out_p[c * s1c] = narrow<P>(fi_site_chan<P, I>(s, fs, L, T, R, Bm, W, H, plane0 + c * s1c, s1h, tap_p, s3c)); \
+                out_p[c * s1c] = narrow<P>(fi_site_chan<P, I, TP>(s, fs, L, T, R, Bm, W, H, plane0 + c * s1c, s1h, tap_p, s3c)); \
         } else {                                                                                                      \
             const st_t<P> *p = plane0 + (int64_t)y * s1h + x;                                                         \
             for (int c = 0; c < nch; c++) out_p[c * s1c] = p[c * s1c];                                                \
@@ -153,7 +154,13 @@ template <class P, class FT>
 __device__ __noinline__ void fi_site_scalar_lp(int x, int y, int W, int H, int nch, int fs, const st_t<P> *plane0,
                                                int64_t s1c, int s1h, const st_t<FT> *flow_p, int64_t s2c,
                                                const st_t<P> *tap_p, int64_t s3c, st_t<P> *out_p)
-MEMC_FI_SITE_SCALAR_BODY(P, FT, int64_t)
+MEMC_FI_SITE_SCALAR_BODY(P, FT, int64_t, P)
+// the same for an image and an output of storage P beside taps of storage TP (the mixed forward, libmemc_hip_mx.so)
+template <class P, class FT, class TP>
+__device__ __noinline__ void fi_site_scalar_mx(int x, int y, int W, int H, int nch, int fs, const st_t<P> *plane0,
+                                               int64_t s1c, int s1h, const st_t<FT> *flow_p, int64_t s2c,
+                                               const st_t<TP> *tap_p, int64_t s3c, st_t<P> *out_p)
+MEMC_FI_SITE_SCALAR_BODY(P, FT, int64_t, TP)
 
 // The per-site backward helpers below are written once over the storage of their tensors (memc_lp.hpp): P for the image,
 // the taps and the tap gradient, FT for the flow and its gradient, GT for gradoutput; the image gradient is always fp32

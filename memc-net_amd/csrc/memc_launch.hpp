@@ -21,13 +21,14 @@ struct Plane {
 inline Plane plane(int sb, int sc, int sh) { return {(int64_t)sb, (int64_t)sc, sh}; }          // the fp32 launcher ABI
 inline Plane plane(const memc_tensor4 *t) { return {t->stride[0], t->stride[1], (int)t->stride[2]}; }
 
-// FilterInterpolation forward.  s1: input1 and output; s2: the flow; s3: the filter taps.
-template <class T = float, class FT = T>
+// FilterInterpolation forward.  s1: input1 and output; s2: the flow; s3: the filter taps.  IT: the storage of input1 and the
+// output where it is not the taps' (the mixed library: float beside half taps).
+template <class T = float, class FT = T, class IT = T>
 struct FiFwdCall {
     hipStream_t stream;
     int w, h, channel, batch, filter_size;
     Plane s1, s2, s3;
-    const T *in1;  const FT *flow;  const T *filt;  T *out;
+    const IT *in1;  const FT *flow;  const T *filt;  IT *out;
 };
 
 // FilterInterpolation backward.  s1: input1, gradoutput and gradinput1 (always fp32: the tiles' flushes add into it; NULL:

@@ -107,12 +107,16 @@ __device__ __forceinline__ f32x4 ld4_cached(const st_t<S> *p)
     if constexpr (sizeof(st_t<S>) == 4) return ld_cached4(reinterpret_cast<const float *>(p));
     else return widen4<S>(*reinterpret_cast<const u16x4a *>(p));
 }
-// narrowed quad store (non-temporal: the output is single-use)
+// narrowed quad store (non-temporal: the output is single-use); F32: the quad as it is
 template <class S>
 __device__ __forceinline__ void st4_stream(st_t<S> *p, const f32x4 &v)
 {
-    const u16x4 q = {narrow<S>(v[0]), narrow<S>(v[1]), narrow<S>(v[2]), narrow<S>(v[3])};
-    __builtin_nontemporal_store(q, reinterpret_cast<u16x4a *>(p));
+    if constexpr (sizeof(st_t<S>) == 4) {
+        st_stream4(reinterpret_cast<float *>(p), v);
+    } else {
+        const u16x4 q = {narrow<S>(v[0]), narrow<S>(v[1]), narrow<S>(v[2]), narrow<S>(v[3])};
+        __builtin_nontemporal_store(q, reinterpret_cast<u16x4a *>(p));
+    }
 }
 // the same through wave-uniform base + 32-bit byte offset (ld_stream4_u / st_stream4_u of memc_tile.hpp; F32: those exactly);
 // the store rounds fp32 values (see narrow_f32)
@@ -184,6 +188,33 @@ __device__ __forceinline__ void lp_stage_store(const Region &r, const StageSlot 
             }
         }
     }
+}
+
+// Staging of an image of either storage: F32 planes through memc_tile.hpp's dword-aligned quads, T planes through the
+// 8-byte quads above.  (The mixed kernels of libmemc_hip_mx.so: an fp32 image beside T taps.)
+template <class S, int NCH>
+using ImgStageRegs = std::conditional_t<sizeof(st_t<S>) == 4, StageRegs<NCH>, LpStageRegs<NCH>>;
+
+template <class S, int NCH>
+__device__ __forceinline__ void img_stage_load(const Region &r, const StageSlot &sl, const st_t<S> *const (&plane)[NCH],
+                                               int hstride, ImgStageRegs<S, NCH> &sr)
+{
+    if constexpr (sizeof(st_t<S>) == 4) {
+        int hs[NCH];
+#pragma unroll
+        for (int c = 0; c < NCH; c++) hs[c] = hstride;
+        tile_stage_load_planes<NCH, false>(r, sl, plane, hs, sr);
+    } else {
+        lp_stage_load<NCH>(r, sl, plane, hstride, sr);
+    }
+}
+
+template <class S, int NCH>
+__device__ __forceinline__ void img_stage_store(const Region &r, const StageSlot &sl, const ImgStageRegs<S, NCH> &sr,
+                                                f32x4 *tile)
+{
+    if constexpr (sizeof(st_t<S>) == 4) tile_stage_store<NCH, false>(r, sl, sr, tile);
+    else lp_stage_store<S, NCH>(r, sl, sr, tile);
 }
 
 }  // namespace memc

@@ -21,6 +21,14 @@ per-direction backward launches run on the half kernel of libmemc_hip_lp_grad.so
 16 taps, width a multiple of four), on the half image and taps, with the float32 gradoutput * occlusion (exact: a product
 of two widened halves).  Elsewhere they run the float32 kernel on the widened inputs.  Each gradient comes back in its
 input's dtype.
+
+Mixed precision (what torch.autocast hands over: float32 frames, float16 / bfloat16 taps and occlusions of one dtype): RGB,
+the 4x4 filter and a width that is a multiple of four from 8 on run ONE kernel of libmemc_hip_mx.so on the tensors as they
+are -- the half kernel's float32 arithmetic, the float32 result unrounded -- instead of widening taps, occlusions and flows
+on the host first (112 B per site moved instead of 416).  Where that library declines (a view it cannot read) the call is
+promoted to float32 as before.  The backward widens the saved tensors and runs the float32 backward above, fused
+directions included: the gradients are those of the promoted call, each in its input's dtype.  Any other mix of dtypes is
+promoted by payload_dtype as before.
 """
 import torch
 from torch.autograd import Function
@@ -29,8 +37,9 @@ from torch.autograd.function import once_differentiable
 import my_package._ext.my_lib as my_lib
 import my_package._ext.my_lib_blend_grad as my_lib_blend_grad
 import my_package._ext.my_lib_lp as my_lib_lp
+import my_package._ext.my_lib_mx as my_lib_mx
 from ._common import cast, check, f32c, flow_dtype, payload_dtype, require_gpu
-from .FilterInterpolationLayer import FilterInterpolationLayer, backward_lp, lp_backward_covered
+from .FilterInterpolationLayer import FilterInterpolationLayer, backward_lp, lp_backward_covered, mx_covered
 
 
 def fused_supported(input0, filter0, *others):
@@ -146,11 +155,59 @@ class _FilterInterpolationBlendLpFunction(Function):
         return tuple(g.to(t.dtype) for g, t in zip(grads, saved))
 
 
+def _blend_forward_fp32(args):
+    """the blend of eight contiguous float32 tensors: the fused kernel where it takes the call, else two warps"""
+    if fused_supported(args[0], args[4], args[1], args[2], args[3], args[5], args[6], args[7]):
+        output = torch.empty_like(args[0])                   # every element is written
+        check(my_lib.FilterInterpolationBlendLayer_gpu_forward(*args, output),
+              "FilterInterpolationBlendLayer_gpu_forward")
+        return output
+    return args[6] * _warp(args[0], args[2], args[4]) + args[7] * _warp(args[1], args[3], args[5])
+
+
+class _FilterInterpolationBlendMxFunction(Function):
+    """float32 images, float16 / bfloat16 taps and occlusions, flows in float32 or that dtype: forward on libmemc_hip_mx.so
+    (where it declines: promoted to float32, the float32 kernels); backward: the promoted call's, on the widened tensors"""
+
+    @staticmethod
+    def forward(ctx, input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):
+        args = tuple(t.contiguous() for t in (input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1))
+        output = torch.empty_like(args[0])                   # every element is written
+        err = my_lib_mx.FilterInterpolationBlendLayer_gpu_forward_mx(*args, output)
+        if err == 1:                                         # declined, nothing touched: the promoted route
+            output = _blend_forward_fp32(tuple(t.float() for t in args))
+        else:
+            check(err, "FilterInterpolationBlendLayer_gpu_forward_mx")
+        ctx.save_for_backward(*args)
+        return output
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gradoutput):
+        saved = ctx.saved_tensors
+        grads = _blend_backward(tuple(t.float() for t in saved), f32c(gradoutput),       # (contiguous already)
+                                needs_image_grad=ctx.needs_input_grad[:2])
+        return tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, saved))
+
+
+def blend_mx_covered(input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):
+    """The mixed call libmemc_hip_mx.so takes (include/memc_warp_mx.h): float32 images, taps and occlusions of ONE half
+    dtype, the two flows of one dtype (float32 or that one), RGB, 16 taps, a width that is a multiple of four from 8 on"""
+    t = filter0.dtype
+    return (mx_covered(input0, filter0) and input2.dtype == torch.float32 and input2.shape == input0.shape and
+            all(x.dtype == t for x in (filter1, occlusion0, occlusion1)) and
+            occlusion0.size(1) == 1 and occlusion1.size(1) == 1 and flow_dtype(flow0, t) == flow_dtype(flow1, t))
+
+
 class FilterInterpolationBlendLayer(object):
     """`FilterInterpolationBlendLayer()(input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1)`"""
 
     def __call__(self, input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):
         require_gpu("FilterInterpolationBlendLayer", input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1)
+        if blend_mx_covered(input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):
+            fdt = flow_dtype(flow0, filter0.dtype)
+            return _FilterInterpolationBlendMxFunction.apply(input0, input2, cast(flow0, fdt), cast(flow1, fdt), filter0,
+                                                             filter1, occlusion0, occlusion1)
         dtype = payload_dtype(input0, input2, filter0, filter1, occlusion0, occlusion1)
         if dtype != torch.float32:
             fdt = flow_dtype(flow0, dtype) if flow_dtype(flow0, dtype) == flow_dtype(flow1, dtype) else torch.float32

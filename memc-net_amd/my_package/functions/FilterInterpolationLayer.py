@@ -18,6 +18,12 @@ Differences, all deliberate:
     as the float32 backward on the widened inputs, each flow / tap gradient rounded once, the image gradient an fp32
     buffer rounded afterwards.  Any other half call widens the saved inputs to float32, runs the float32 backward
     kernels and returns each gradient in its input's dtype.
+  * mixed precision (what torch.autocast hands over: a float32 image, float16 / bfloat16 taps): three channels, the 4x4
+    filter and a width that is a multiple of four from 8 on run ONE kernel of libmemc_hip_mx.so on the tensors as they are
+    -- the half kernels' float32 arithmetic, the float32 result unrounded -- instead of widening the taps and the flow on
+    the host first (60 B per site moved instead of 204).  Where that library declines (a view it cannot read) the call is
+    promoted to float32 as before.  The backward widens the saved tensors and runs the float32 backward: the gradients
+    are those of the promoted call, each in its input's dtype.  Any other mixed call is promoted as before.
 """
 import torch
 from torch.autograd import Function
@@ -26,7 +32,8 @@ from torch.autograd.function import once_differentiable
 import my_package._ext.my_lib as my_lib
 import my_package._ext.my_lib_lp as my_lib_lp
 import my_package._ext.my_lib_lp_grad as my_lib_lp_grad
-from ._common import cast, check, f32c, flow_dtype, payload_dtype, require_gpu
+import my_package._ext.my_lib_mx as my_lib_mx
+from ._common import LOWP, cast, check, f32c, flow_dtype, payload_dtype, require_gpu
 
 
 class _FilterInterpolationFunction(Function):
@@ -144,12 +151,46 @@ class _FilterInterpolationLpFunction(Function):
         return tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, saved))
 
 
+def mx_covered(image, taps):
+    """The mixed call libmemc_hip_mx.so takes (include/memc_warp_mx.h): a float32 image, half taps, and the shapes of
+    lp_backward_covered.  (Views it declines all the same come back as return code 1.)"""
+    return image.dtype == torch.float32 and taps.dtype in LOWP and lp_backward_covered(image, taps)
+
+
+class _FilterInterpolationMxFunction(Function):
+    """a float32 image, float16 / bfloat16 taps, the flow in float32 or the taps' dtype: forward on libmemc_hip_mx.so
+    (where it declines: promoted to float32, the float32 kernel); backward: the promoted call's, on the widened tensors"""
+
+    @staticmethod
+    def forward(ctx, input1, input2, input3):
+        input1, input2, input3 = input1.contiguous(), input2.contiguous(), input3.contiguous()
+        output = torch.empty_like(input1)                    # every element is written
+        err = my_lib_mx.FilterInterpolationLayer_gpu_forward_mx(input1, input2, input3, output)
+        if err == 1:                                         # declined, nothing touched: the promoted route
+            err = my_lib.FilterInterpolationLayer_gpu_forward(input1, input2.float(), input3.float(), output)
+            check(err, "FilterInterpolationLayer_gpu_forward")
+        else:
+            check(err, "FilterInterpolationLayer_gpu_forward_mx")
+        ctx.save_for_backward(input1, input2, input3)
+        return output
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gradoutput):
+        saved = ctx.saved_tensors
+        input1, input2, input3 = (t.float() for t in saved)  # contiguous already
+        grads = _backward_fp32(input1, input2, input3, f32c(gradoutput), ctx.needs_input_grad[0])
+        return tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, saved))
+
+
 class FilterInterpolationLayer(object):
     def __init__(self):
         super(FilterInterpolationLayer, self).__init__()
 
     def __call__(self, input1, input2, input3):
         require_gpu("FilterInterpolationLayer", input1, input2, input3)
+        if mx_covered(input1, input3):
+            return _FilterInterpolationMxFunction.apply(input1, cast(input2, flow_dtype(input2, input3.dtype)), input3)
         dtype = payload_dtype(input1, input3)
         if dtype == torch.float32:
             return _FilterInterpolationFunction.apply(cast(input1, dtype), cast(input2, dtype), cast(input3, dtype))

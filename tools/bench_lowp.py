@@ -1,14 +1,22 @@
 #!/usr/bin/env python
 """tools/bench_lowp.py -- fp32 / fp16 / bf16 adaptive warps side by side, in one process.
 
-    python tools/bench_lowp.py [--rounds 3] [--iters 10] [--json out.json]
+    python tools/bench_lowp.py [--rounds 3] [--iters 10] [--json out.json] [--only lowp|mixed]
 
 Cases: FilterInterpolation forward 32x3x720x1280 (smooth flow; fp32 flow and half flow), the fused dual warp + occlusion
 blend 32x3x720x1280, and FilterInterpolation forward 8x64x720x1280 (the context warp).  Each case times fp32 (libmemc_hip.so),
 fp16 and bf16 (libmemc_hip_lp.so) ALTERNATELY, round after round, so that clock and thermal drift fall on all three alike;
 every launch rotates over enough input sets to cycle more than 1 GB, as bench.py does (no set fits the 256 MiB Infinity
 Cache).  Printed per row: median launch time over the rounds, algorithmic bytes per site and per launch, TB/s, the fraction
-of the 8 TB/s HBM peak and the ratio of the time to fp32's."""
+of the 8 TB/s HBM peak and the ratio of the time to fp32's.
+
+Mixed rows (--only mixed, or after the others): the call torch.autocast makes -- fp32 frames, fp16 / bf16 taps and occlusions,
+the flow in fp32 or that dtype -- on the RGB warp and the fused blend at 8x3x256x448 and 32x3x720x1280, each AS THE LAYER RUNS
+IT, allocations included: `mixed` (libmemc_hip_mx.so on the tensors as they are) against `promoted` (the .to(float32) casts of
+taps, occlusions and half flows, then libmemc_hip.so: the layers' route before that library existed), and for the blend
+`fp32` (libmemc_hip.so on fp32 inputs, for orientation).  The arms run in ALTERNATING windows of 8 timed launches (bursts of
+10 for the small shape), six windows each; per row the median of the window medians, the spread (largest minus smallest
+window median) and the bytes per site the route moves."""
 import argparse
 import json
 import math
@@ -111,8 +119,93 @@ def run_case(name, op, shape, half_flow, rounds, iters):
     return rows
 
 
+# ---- mixed precision: fp32 frames beside half taps ---------------------------------------------------------------------
+def mixed_bytes_per_site(op, route, half_flow):
+    """bytes a route moves per site, from the layouts: (casts, kernel)"""
+    f = 2 if half_flow else 4
+    if op == "fi":
+        if route == "mixed":
+            return 0, 12 + 2 * f + 32 + 12
+        casts = 16 * (2 + 4) + (2 * (2 + 4) if half_flow else 0)
+        return casts, 96
+    if route == "mixed":
+        return 0, 24 + 4 * f + 64 + 4 + 12
+    if route == "fp32":
+        return 0, 188
+    casts = 2 * 16 * (2 + 4) + 2 * (2 + 4) + (4 * (2 + 4) if half_flow else 0)
+    return casts, 188
+
+
+def _mixed_arm(op, route, sets):
+    import my_package._ext.my_lib as my_lib
+    import my_package._ext.my_lib_mx as my_lib_mx
+    state = {"i": 0}
+    names = ("x", "flow", "filt") if op == "fi" else ("x", "x2", "flow", "flow2", "filt", "filt2", "occ0", "occ1")
+    f32 = my_lib.FilterInterpolationLayer_gpu_forward if op == "fi" else my_lib.FilterInterpolationBlendLayer_gpu_forward
+    mx = (my_lib_mx.FilterInterpolationLayer_gpu_forward_mx if op == "fi"
+          else my_lib_mx.FilterInterpolationBlendLayer_gpu_forward_mx)
+
+    def call():
+        i = state["i"]
+        state["i"] = (i + 1) % len(sets)
+        args = [sets[i][n] for n in names]
+        out = torch.empty_like(args[0])                      # the layer allocates its output per call
+        if route == "mixed":
+            err = mx(*args, out)
+        else:                                                # promoted: the casts are per-call allocations and passes
+            err = f32(*[a.to(torch.float32) for a in args], out)
+        if err != 0:
+            raise RuntimeError("%s %s returned %d" % (op, route, err))
+
+    return call
+
+
+def run_mixed(shape, windows=6, iters=8):
+    B, C, H, W = shape
+    sites = B * H * W
+    burst = 10 if sites < (1 << 21) else 1
+    n = max(2, math.ceil(ROTATE_BYTES / (sites * 112)))
+    base = _sets(B, C, H, W, n, True, seed=8765)
+    rows = []
+    for op in ("fi", "blend"):
+        for tname, dt in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
+            for half_flow in (False, True):
+                ft = dt if half_flow else torch.float32
+                mixed_sets = [{k: (v if k.startswith("x") else v.to(ft if k.startswith("flow") else dt).contiguous())
+                               for k, v in s.items()} for s in base]
+                arms = [("mixed", mixed_sets), ("promoted", mixed_sets)] + ([("fp32", base)] if op == "blend" else [])
+                calls = {r: _mixed_arm(op, r, ss) for r, ss in arms}
+                meds = {r: [] for r, _ in arms}
+                for _ in range(windows):
+                    for r, _ss in arms:
+                        med, _mn = time_launches(calls[r], warmup=2, iters=iters, burst=burst)
+                        meds[r].append(med)
+                for r, _ss in arms:
+                    casts, kern = mixed_bytes_per_site(op, r, half_flow)
+                    t = statistics.median(meds[r])
+                    rows.append({"case": "%s %dx%dx%dx%d" % (op, B, C, H, W), "taps": tname,
+                                 "flow": str(ft).replace("torch.", ""), "route": r, "us": round(t * 1e6, 1),
+                                 "windows_us": [round(m * 1e6, 1) for m in meds[r]],
+                                 "spread_us": round((max(meds[r]) - min(meds[r])) * 1e6, 1),
+                                 "bytes_per_site": casts + kern, "cast_bytes_per_site": casts,
+                                 "TBps_moved": round((casts + kern) * sites / t / 1e12, 3), "input_sets": n, "burst": burst})
+                    print("%-22s %-4s flow %-8s %-8s %9.1f us  spread %5.1f us  %3d B/site (%3d casts)  %6.3f TB/s moved"
+                          "   windows: %s" % (rows[-1]["case"], tname, rows[-1]["flow"], r, rows[-1]["us"],
+                                              rows[-1]["spread_us"], casts + kern, casts, rows[-1]["TBps_moved"],
+                                              " ".join("%.1f" % w for w in rows[-1]["windows_us"])), flush=True)
+                m, p = rows[-len(arms)], rows[-len(arms) + 1]
+                print("    mixed / promoted: x%.3f (%.1f us saved, larger spread %.1f us)" % (
+                    m["us"] / p["us"], p["us"] - m["us"], max(m["spread_us"], p["spread_us"])), flush=True)
+                del mixed_sets, calls
+                torch.cuda.empty_cache()
+    del base
+    torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--only", choices=("lowp", "mixed"), default=None, help="the half rows or the mixed rows alone")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--json", default=None)
@@ -122,12 +215,15 @@ def main():
              ("blend 32x3x720x1280", "blend", (32, 3, 720, 1280), False),
              ("fi_fwd 8x64x720x1280", "fi", (8, 64, 720, 1280), False)]
     rows = []
-    for name, op, shape, half_flow in cases:
+    for name, op, shape, half_flow in ([] if a.only == "mixed" else cases):
         for r in run_case(name, op, shape, half_flow, a.rounds, a.iters):
             rows.append(r)
             print("%-32s %-5s flow %-8s %9.1f us  %3d B/site  %6.3f TB/s  %.3f of 8 TB/s  x%.3f vs fp32" % (
                 r["case"], r["dtype"], r["flow"], r["us"], r["bytes_per_site"], r["TBps"], r["frac_8TBps"],
                 r["ratio_to_fp32"]), flush=True)
+    if a.only != "lowp":
+        for shape in ((8, 3, 256, 448), (32, 3, 720, 1280)):
+            rows += run_mixed(shape)
     if a.json:
         with open(a.json, "w") as f:
             json.dump(rows, f, indent=1)
