@@ -29,7 +29,8 @@ __global__ __launch_bounds__(NT, RAG ? 1 : (PART == 0 || !kPartThree ? 2 : 3)) v
     const float *__restrict__ gout, float *__restrict__ gin1, float *__restrict__ gin2,
     float *__restrict__ gin3)
 {
-    using P = F32;                             // storage of the image / taps, the flow, gradoutput (memc_lp.hpp)
+    using P = F32;                             // storage of the taps, the image, the flow, gradoutput (memc_lp.hpp)
+    using I = P;
     using FT = F32;
     using GT = F32;
 #include "fi_bwd_c3_body.inc"

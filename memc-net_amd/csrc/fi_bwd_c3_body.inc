@@ -1,10 +1,12 @@
 // fi_bwd_c3_body.inc -- the body of the RGB (C == 3, fs == 4) LDS-tiled FilterInterpolation backward, included INSIDE
 // the kernels that run it:
-//   fi_bwd_c3_pk   (fi_bwd_c3.hip, libmemc_hip.so)            P = FT = GT = F32;
-//   fi_bwd_c3_lp   (lp_fi_bwd_c3.hip, libmemc_hip_lp_grad.so) P = F16 / BF16, FT and GT = F32 or P, RAG = false.
-// The including kernel defines the storage tags P (image, taps, tap gradient), FT (flow, flow gradient) and GT
+//   fi_bwd_c3_pk   (fi_bwd_c3.hip, libmemc_hip.so)            I = P = FT = GT = F32;
+//   fi_bwd_c3_lp   (lp_fi_bwd_c3.hip, libmemc_hip_lp_grad.so) I = P = F16 / BF16, FT and GT = F32 or P, RAG = false;
+//   fi_bwd_c3_mx   (mx_fi_bwd_c3.hip, libmemc_hip_mx_grad.so) I = GT = F32, P = F16 / BF16, FT = F32 or P, RAG = false.
+// The including kernel defines the storage tags I (image), P (taps, tap gradient), FT (flow, flow gradient) and GT
 // (gradoutput), the compile-time TR, NT, PART and RAG, and the parameters W, H, tiles_x, tiles_y, batch, s1b .. s3h, in1,
-// flow, filt, gout, gin1 (fp32: ADDED into, flushed with atomics), gin2, gin3.  Every global load widens exactly
+// flow, filt, gout, gin1 (fp32: ADDED into, flushed with atomics), gin2, gin3.  Only the staging of the image box and
+// the per-site paths from global memory read the image: with I = P they are the *_lp helpers (memc_fi.hpp), else *_mx.  Every global load widens exactly
 // (memc_lp.hpp) and every stored gradient is rounded once: the LDS image, the packed planes and the arithmetic are the
 // same for every storage.  (Included text rather than an always-inline function: the extra inlined call level changes
 // the compiler's vectorisation and contraction choices, and the fp32 kernel keeps its machine code bit for bit.)
@@ -86,7 +88,7 @@
     const unsigned packed = PART != 2 ? pk_packed_sites(ps, sbits, g.valid) : 0u;
     const unsigned outl = PART != 2 ? pk_outlier_sites(ps, sbits, g.valid) : 0u;
     const int mode = ps.any;                   // 0: no packed site has anything to add (workgroup-uniform)
-    const st_t<P> *in_b = in1 + b * s1b;
+    const st_t<I> *in_b = in1 + b * s1b;
     float *gin1_b = gin1 + b * s1b;
     unsigned done = 0;
     trace_mark<TR>(2);                                         // bounding box known
@@ -114,10 +116,14 @@
                 if constexpr (kF32)
                     fi_bwd_site_taps(x + j, y, W, H, in_b, s1c, s1h, flow_b + o2 / 4 + j, gin2_b + o2 / 4 + j, s2c,
                                      filt_b + o3 / 4 + j, gin3_b + o3 / 4 + j, s3c, gout_b + o1 / 4 + j);
-                else
+                else if constexpr (std::is_same_v<I, P>)
                     fi_bwd_site_taps_lp<P, FT, GT>(x + j, y, W, H, in_b, s1c, s1h, flow_b + o2 / zF + j,
                                                    gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j, gin3_b + o3 / zP + j,
                                                    s3c, gout_b + o1 / zG + j);
+                else
+                    fi_bwd_site_taps_mx<P, FT, GT, I>(x + j, y, W, H, in_b, s1c, s1h, flow_b + o2 / zF + j,
+                                                      gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j,
+                                                      gin3_b + o3 / zP + j, s3c, gout_b + o1 / zG + j);
             }
         }
     };
@@ -130,17 +136,22 @@
     done |= fast;
     const StageSlot sl = stage_slots<NT>(r);
     // the image box: fp32 quads, or half quads as two packed dwords (widened when they are written to the LDS)
-    StageRegsOf<P> sr;
-    if (PART != 1) fi_bwd_stage_load<P, RAG>(r, sl, in_b, s1c, s1h, sr);   // in flight during adds and flush
+    StageRegsOf<I> sr;
+    if (PART != 1) fi_bwd_stage_load<I, RAG>(r, sl, in_b, s1c, s1h, sr);   // in flight during adds and flush
     if (PART != 2 && mode == 1) {
         if (bi > 0) {                      // (band 0: zeroed at the top, ordered by the barrier of tile_bbox)
             zero_planes(r.h * r.pitch);
             __syncthreads();
         }
-        fi_bwd_adds_pk(r, fast & packed, g, tp, go, ps.sa, ps.sb, accA, accB, W, H);
+        // (a mixed image keeps fp32 staging registers beside the half kernel's 64-bit store addresses: with the scaled
+        // gradoutput -- 12 products -- hoisted out of the band loop as well, the whole backward spills; opaque scales
+        // keep the products inside the loop)
+        float sa = ps.sa, sb = ps.sb;
+        if constexpr (!std::is_same_v<I, P>) asm volatile("" : "+v"(sa), "+v"(sb));
+        fi_bwd_adds_pk(r, fast & packed, g, tp, go, sa, sb, accA, accB, W, H);
         __syncthreads();
         if (bi == 0) trace_mark<TR>(3);                    // accumulated
-        if (PART != 1) fi_bwd_stage_touch<P>(sr);      // the staged rows have landed long ago: take the wait
+        if (PART != 1) fi_bwd_stage_touch<I>(sr);      // the staged rows have landed long ago: take the wait
                                                            // here, not behind the flush's atomics
         pk_flush<NT>(r, accA, accB, ps.inv, gin1_b, s1c, s1h);
         if (PART != 1) __syncthreads();    // the planes have been read: the LDS becomes the image
@@ -148,7 +159,7 @@
     }
     if (PART != 2 && (fast & outl)) image_atomics(fast & outl);
     if (PART != 1) {
-        fi_bwd_stage_store<P, RAG>(r, sl, sr, tile);
+        fi_bwd_stage_store<I, RAG>(r, sl, sr, tile);
         __syncthreads();
         if (bi == 0) trace_mark<TR>(5);                    // image staged
         phase1(r, fast);
@@ -174,13 +185,25 @@
             // PART 0 and PART 2 sum gradinput2 in different orders (fi_bwd_site_scalar vs fi_bwd_site_taps): the half
             // kernel takes the one the fp32 library takes for the same call
             static_assert(PART != 1, "half storage: PART 0 or 2");
-            if (PART == 0)
-                fi_bwd_site_scalar_lp<P, FT, GT>(x + j, y, W, H, 3, 4, in_b, gin1_b, s1c, s1h, flow_b + o2 / zF + j,
-                                                 gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j, gin3_b + o3 / zP + j,
-                                                 s3c, gout_b + o1 / zG + j);
-            else
-                fi_bwd_site_taps_lp<P, FT, GT>(x + j, y, W, H, in_b, s1c, s1h, flow_b + o2 / zF + j, gin2_b + o2 / zF + j,
-                                               s2c, filt_b + o3 / zP + j, gin3_b + o3 / zP + j, s3c, gout_b + o1 / zG + j);
+            if constexpr (std::is_same_v<I, P>) {
+                if (PART == 0)
+                    fi_bwd_site_scalar_lp<P, FT, GT>(x + j, y, W, H, 3, 4, in_b, gin1_b, s1c, s1h, flow_b + o2 / zF + j,
+                                                     gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j,
+                                                     gin3_b + o3 / zP + j, s3c, gout_b + o1 / zG + j);
+                else
+                    fi_bwd_site_taps_lp<P, FT, GT>(x + j, y, W, H, in_b, s1c, s1h, flow_b + o2 / zF + j,
+                                                   gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j, gin3_b + o3 / zP + j,
+                                                   s3c, gout_b + o1 / zG + j);
+            } else {
+                if (PART == 0)
+                    fi_bwd_site_scalar_mx<P, FT, GT, I>(x + j, y, W, H, 3, 4, in_b, gin1_b, s1c, s1h, flow_b + o2 / zF + j,
+                                                        gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j,
+                                                        gin3_b + o3 / zP + j, s3c, gout_b + o1 / zG + j);
+                else
+                    fi_bwd_site_taps_mx<P, FT, GT, I>(x + j, y, W, H, in_b, s1c, s1h, flow_b + o2 / zF + j,
+                                                      gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j,
+                                                      gin3_b + o3 / zP + j, s3c, gout_b + o1 / zG + j);
+            }
         }
     }
 }

@@ -31,6 +31,7 @@ __global__ __launch_bounds__(256, 2) void fi_bwd_c3_lp(
     const st_t<GT> *__restrict__ gout, float *__restrict__ gin1, st_t<FT> *__restrict__ gin2,
     st_t<P> *__restrict__ gin3)
 {
+    using I = P;                               // the image is stored as the taps are
     constexpr bool TR = false;                 // (timestamps: the fp32 measurement build only)
     constexpr int NT = 256;
     constexpr bool RAG = false;                // widths that are a multiple of four

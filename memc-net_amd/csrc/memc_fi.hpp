@@ -1,5 +1,6 @@
 // memc_fi.hpp -- the per-site device helpers of every FilterInterpolation kernel, forward and backward, fp32 and half
-// storage (filter_interpolation.hip, fi_bwd_c3.hip, fi_bwd_cn.hip, lp_filter_interpolation.hip, lp_fi_bwd_c3.hip, arms/):
+// storage (filter_interpolation.hip, fi_bwd_c3.hip, fi_bwd_cn.hip, lp_filter_interpolation.hip, lp_fi_bwd_c3.hip,
+// mx_filter_interpolation.hip, mx_fi_bwd_c3.hip, arms/):
 // the geometry of a lane's four sites, the LDS gather, the one-site paths from global memory.
 //
 // What the fp32 kernels and their half twins share is written ONCE here, as a macro wherever a shared always-inline
@@ -162,9 +163,10 @@ __device__ __noinline__ void fi_site_scalar_mx(int x, int y, int W, int H, int n
                                                const st_t<TP> *tap_p, int64_t s3c, st_t<P> *out_p)
 MEMC_FI_SITE_SCALAR_BODY(P, FT, int64_t, TP)
 
-// The per-site backward helpers below are written once over the storage of their tensors (memc_lp.hpp): P for the image,
-// the taps and the tap gradient, FT for the flow and its gradient, GT for gradoutput; the image gradient is always fp32
-// (it takes atomics).  Every load widens exactly, every result is rounded once when it is stored: for the same (widened)
+// The per-site backward helpers below are written once over the storage of their tensors (memc_lp.hpp): P for the taps
+// and the tap gradient, IM for the image (P itself in the fp32 functions and the *_lp templates; the *_mx templates of
+// libmemc_hip_mx_grad.so take it apart: an fp32 image beside half taps), FT for the flow and its gradient, GT for
+// gradoutput; the image gradient is always fp32 (it takes atomics).  Every load widens exactly, every result is rounded once when it is stored: for the same (widened)
 // inputs a half instantiation computes the fp32 one's values.  The bodies are macros, expanded in the fp32 functions of
 // libmemc_hip.so (fi_bwd_site_scalar, fi_bwd_site_taps) and in the *_lp templates of libmemc_hip_lp_grad.so: a forwarding
 // call to a shared always-inline template would be the same source but not the same machine code (the inlined call
@@ -175,7 +177,7 @@ MEMC_FI_SITE_SCALAR_BODY(P, FT, int64_t, TP)
 // The tap gradient is a sum over the channels: fp32 taps accumulate it in memory (g3[k] +=, exact in fp32); half taps
 // may not (each add would be rounded to T), so their sums are formed in a register from the same terms in the same
 // order, behind the channel loop, and stored once.
-#define MEMC_FI_BWD_SITE_SCALAR_BODY(P, FT, GT)                                                                       \
+#define MEMC_FI_BWD_SITE_SCALAR_BODY(P, FT, GT, IM)                                                                   \
     {                                                                                                                 \
         constexpr bool kMem = sizeof(st_t<P>) == 4;                                                                   \
         const float fx = widen_f32<FT>(flow_p[0]), fy = widen_f32<FT>(flow_p[s2c]);                                   \
@@ -185,7 +187,7 @@ MEMC_FI_SITE_SCALAR_BODY(P, FT, int64_t, TP)
         float botx = 0.0f, boty = 0.0f;                                                                               \
         const float gam_x = 1.0f - s.b, gam_y = 1.0f - s.a;                                                           \
         for (int c = 0; c < C; c++) {                                                                                 \
-            const st_t<P> *p = in_b + c * s1c;                                                                        \
+            const st_t<IM> *p = in_b + c * s1c;                                                                       \
             float *q = gin1_b + c * s1c;                                                                              \
             const float g = widen_f32<GT>(gout_p[c * s1c]);                                                           \
             for (int j = T; j < Bm; j++) {                                                                            \
@@ -201,10 +203,10 @@ MEMC_FI_SITE_SCALAR_BODY(P, FT, int64_t, TP)
                     }                                                                                                 \
                 }                                                                                                     \
             }                                                                                                         \
-            const float TL = fi_quad_sum<P>(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, L, s.ix);                    \
-            const float TR = fi_quad_sum<P>(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, s.ix + 1, R - 1);            \
-            const float BL = fi_quad_sum<P>(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, L, s.ix);           \
-            const float BR = fi_quad_sum<P>(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, s.ix + 1, R - 1);   \
+            const float TL = fi_quad_sum<IM, int, P>(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, L, s.ix);           \
+            const float TR = fi_quad_sum<IM, int, P>(p, s1h, W, H, tap_p, s3c, fs, L, T, T, s.iy, s.ix + 1, R - 1);   \
+            const float BL = fi_quad_sum<IM, int, P>(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, L, s.ix);  \
+            const float BR = fi_quad_sum<IM, int, P>(p, s1h, W, H, tap_p, s3c, fs, L, T, s.iy + 1, Bm - 1, s.ix + 1, R - 1); \
             float tmp = 0.0f;                                                                                         \
             tmp += gam_x * (TR - TL);                                                                                 \
             tmp += (1.0f - gam_x) * (BR - BL);                                                                        \
@@ -224,12 +226,12 @@ MEMC_FI_SITE_SCALAR_BODY(P, FT, int64_t, TP)
                         const float g = widen_f32<GT>(gout_p[c * s1c]);                                               \
                         const float wgt = (j <= s.iy) ? ((i <= s.ix) ? g * (1 - s.a) * (1 - s.b) : g * s.a * (1 - s.b)) \
                                                       : ((i <= s.ix) ? g * (1 - s.a) * s.b : g * s.a * s.b);          \
-                        const st_t<P> *p = in_b + c * s1c;                                                            \
+                        const st_t<IM> *p = in_b + c * s1c;                                                           \
                         /* the fp32 function's `g3[k] += wgt * p` is a rounded product and an add (v_mul, v_add: its */ \
                         /* store of channel 0 sits between them); here the loop unrolls and the compiler would       */ \
                         /* contract the adds into fmas -- a last-bit difference that flips about one rounding to T   */ \
                         /* in 2^13.  The asm keeps the product a value of its own.                                   */ \
-                        float t3 = wgt * widen_f32<P>(p[jj + ii]);                                                    \
+                        float t3 = wgt * widen_f32<IM>(p[jj + ii]);                                                   \
                         asm volatile("" : "+v"(t3));                                                                  \
                         if (c == 0) a3 = t3; else a3 += t3;                                                           \
                     }                                                                                                 \
@@ -244,31 +246,38 @@ __device__ __noinline__ inline void fi_bwd_site_scalar(int x, int y, int W, int 
                                                 const float *in_b, float *gin1_b, int64_t s1c, int s1h,
                                                 const float *flow_p, float *g2, int64_t s2c,
                                                 const float *tap_p, float *g3, int64_t s3c, const float *gout_p)
-MEMC_FI_BWD_SITE_SCALAR_BODY(F32, F32, F32)
+MEMC_FI_BWD_SITE_SCALAR_BODY(F32, F32, F32, F32)
 template <class P, class FT, class GT>
 __device__ __noinline__ void fi_bwd_site_scalar_lp(int x, int y, int W, int H, int C, int fs, const st_t<P> *in_b,
                                                    float *gin1_b, int64_t s1c, int s1h, const st_t<FT> *flow_p,
                                                    st_t<FT> *g2, int64_t s2c, const st_t<P> *tap_p, st_t<P> *g3,
                                                    int64_t s3c, const st_t<GT> *gout_p)
-MEMC_FI_BWD_SITE_SCALAR_BODY(P, FT, GT)
+MEMC_FI_BWD_SITE_SCALAR_BODY(P, FT, GT, P)
+// the same with an image of storage IM beside taps of storage P (the mixed backward, libmemc_hip_mx_grad.so)
+template <class P, class FT, class GT, class IM>
+__device__ __noinline__ void fi_bwd_site_scalar_mx(int x, int y, int W, int H, int C, int fs, const st_t<IM> *in_b,
+                                                   float *gin1_b, int64_t s1c, int s1h, const st_t<FT> *flow_p,
+                                                   st_t<FT> *g2, int64_t s2c, const st_t<P> *tap_p, st_t<P> *g3,
+                                                   int64_t s3c, const st_t<GT> *gout_p)
+MEMC_FI_BWD_SITE_SCALAR_BODY(P, FT, GT, IM)
 #undef MEMC_FI_BWD_SITE_SCALAR_BODY
 
 
 // gradinput3 and gradinput2 of ONE site straight from global memory (mixed quads of the tiled RGB backward: some of a
 // lane's four sites belong to another band or are invalid).  Assigns both, like the tiled path; the image
 // gradient of such a site still goes through the tile's LDS planes.
-#define MEMC_FI_BWD_SITE_TAPS_BODY(P, FT, GT)                                                                         \
+#define MEMC_FI_BWD_SITE_TAPS_BODY(P, FT, GT, IM)                                                                     \
     {                                                                                                                 \
         const FiSite s = fi_locate(x, y, W, H, widen_f32<FT>(flow_p[0]), widen_f32<FT>(flow_p[s2c]));                 \
         if (!s.valid) return;                                                                                         \
         const float g0 = widen_f32<GT>(gout_p[0]), g1 = widen_f32<GT>(gout_p[s1c]), gc2 = widen_f32<GT>(gout_p[2 * s1c]); \
         float gx = 0.0f, gy = 0.0f;                                                                                   \
         for (int k = 0; k < 4; k++) {                                                                                 \
-            const st_t<P> *row = in_b + (int64_t)clampi(s.iy - 1 + k, H - 1) * s1h;                                   \
+            const st_t<IM> *row = in_b + (int64_t)clampi(s.iy - 1 + k, H - 1) * s1h;                                  \
             for (int m = 0; m < 4; m++) {                                                                             \
-                const st_t<P> *p = row + clampi(s.ix - 1 + m, W - 1);                                                 \
+                const st_t<IM> *p = row + clampi(s.ix - 1 + m, W - 1);                                                \
                 float sv = 0.0f;                                                                                      \
-                sv += g0 * widen_f32<P>(p[0]);  sv += g1 * widen_f32<P>(p[s1c]);  sv += gc2 * widen_f32<P>(p[2 * s1c]); \
+                sv += g0 * widen_f32<IM>(p[0]);  sv += g1 * widen_f32<IM>(p[s1c]);  sv += gc2 * widen_f32<IM>(p[2 * s1c]); \
                 const float wa = m < 2 ? (1 - s.a) : s.a, wb = k < 2 ? (1 - s.b) : s.b;                               \
                 g3[(k * 4 + m) * s3c] = narrow_f32<P>((wa * wb) * sv);                                                \
                 const float st = sv * widen_f32<P>(tap_p[(k * 4 + m) * s3c]);                                         \
@@ -282,12 +291,17 @@ MEMC_FI_BWD_SITE_SCALAR_BODY(P, FT, GT)
 __device__ __noinline__ inline void fi_bwd_site_taps(int x, int y, int W, int H, const float *in_b, int64_t s1c, int s1h,
                                               const float *flow_p, float *g2, int64_t s2c, const float *tap_p,
                                               float *g3, int64_t s3c, const float *gout_p)
-MEMC_FI_BWD_SITE_TAPS_BODY(F32, F32, F32)
+MEMC_FI_BWD_SITE_TAPS_BODY(F32, F32, F32, F32)
 template <class P, class FT, class GT>
 __device__ __noinline__ void fi_bwd_site_taps_lp(int x, int y, int W, int H, const st_t<P> *in_b, int64_t s1c, int s1h,
                                                  const st_t<FT> *flow_p, st_t<FT> *g2, int64_t s2c, const st_t<P> *tap_p,
                                                  st_t<P> *g3, int64_t s3c, const st_t<GT> *gout_p)
-MEMC_FI_BWD_SITE_TAPS_BODY(P, FT, GT)
+MEMC_FI_BWD_SITE_TAPS_BODY(P, FT, GT, P)
+template <class P, class FT, class GT, class IM>
+__device__ __noinline__ void fi_bwd_site_taps_mx(int x, int y, int W, int H, const st_t<IM> *in_b, int64_t s1c, int s1h,
+                                                 const st_t<FT> *flow_p, st_t<FT> *g2, int64_t s2c, const st_t<P> *tap_p,
+                                                 st_t<P> *g3, int64_t s3c, const st_t<GT> *gout_p)
+MEMC_FI_BWD_SITE_TAPS_BODY(P, FT, GT, IM)
 #undef MEMC_FI_BWD_SITE_TAPS_BODY
 
 // gradinput2 / gradinput3 are fully DEFINED by the backward kernels (the Python layer hands them over

@@ -1,7 +1,8 @@
 // memc_fi_bwd_c3.hpp -- the FilterInterpolation backward, RGB (C == 3), fs == 4, LDS-tiled: the pieces of its kernel body
 // (fi_bwd_c3_body.inc), written once over the storage of the tensors (memc_lp.hpp: F32, F16, BF16).
 //   fi_bwd_c3.hip       fi_bwd_c3_pk: fp32 (libmemc_hip.so), the description of the algorithm and its measurements;
-//   lp_fi_bwd_c3.hip    fi_bwd_c3_lp: fp16 / bf16 image and taps, fp32 or half flow and gradoutput (libmemc_hip_lp_grad.so).
+//   lp_fi_bwd_c3.hip    fi_bwd_c3_lp: fp16 / bf16 image and taps, fp32 or half flow and gradoutput (libmemc_hip_lp_grad.so);
+//   mx_fi_bwd_c3.hip    fi_bwd_c3_mx: fp32 image and gradoutput, fp16 / bf16 taps, fp32 or half flow (libmemc_hip_mx_grad.so).
 // The LDS image, the packed planes of the image gradient and the arithmetic are the same for every storage: loads widen
 // exactly, each stored gradient is rounded once.  The fp32 instantiations compile to the machine code they had before the
 // storage was made a parameter (checked by disassembly: profiles/r07_lowp_backward.txt).

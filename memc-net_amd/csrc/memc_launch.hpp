@@ -32,13 +32,14 @@ struct FiFwdCall {
 };
 
 // FilterInterpolation backward.  s1: input1, gradoutput and gradinput1 (always fp32: the tiles' flushes add into it; NULL:
-// not wanted); s2: the flow and gradinput2; s3: the taps and gradinput3.
-template <class T = float, class FT = T, class GT = T>
+// not wanted); s2: the flow and gradinput2; s3: the taps and gradinput3.  IT: the storage of input1 where it is not the
+// taps' (the mixed backward library: float beside half taps).
+template <class T = float, class FT = T, class GT = T, class IT = T>
 struct FiBwdCall {
     hipStream_t stream;
     int w, h, channel, batch, filter_size;
     Plane s1, s2, s3;
-    const T *in1;  const FT *flow;  const T *filt;  const GT *gout;
+    const IT *in1;  const FT *flow;  const T *filt;  const GT *gout;
     float *gin1;  FT *gin2;  T *gin3;
 };
 

@@ -22,8 +22,12 @@ Differences, all deliberate:
     filter and a width that is a multiple of four from 8 on run ONE kernel of libmemc_hip_mx.so on the tensors as they are
     -- the half kernels' float32 arithmetic, the float32 result unrounded -- instead of widening the taps and the flow on
     the host first (60 B per site moved instead of 204).  Where that library declines (a view it cannot read) the call is
-    promoted to float32 as before.  The backward widens the saved tensors and runs the float32 backward: the gradients
-    are those of the promoted call, each in its input's dtype.  Any other mixed call is promoted as before.
+    promoted to float32 as before.  The backward runs ONE kernel of libmemc_hip_mx_grad.so on the saved tensors as they
+    are (the float32 image, the half taps, the float32 gradient of the float32 output): the float32 backward's arithmetic
+    on the widened inputs, each flow / tap gradient rounded once, the image gradient (only where autograd asks for it)
+    float32 -- bit for bit the flow and tap gradients of the promoted call, without its widening and narrowing passes
+    (104 B per site moved instead of about 360).  Where that library declines, the saved tensors are widened and the
+    float32 backward runs, as before.  Any other mixed call is promoted as before.
 """
 import torch
 from torch.autograd import Function
@@ -33,6 +37,7 @@ import my_package._ext.my_lib as my_lib
 import my_package._ext.my_lib_lp as my_lib_lp
 import my_package._ext.my_lib_lp_grad as my_lib_lp_grad
 import my_package._ext.my_lib_mx as my_lib_mx
+import my_package._ext.my_lib_mx_grad as my_lib_mx_grad
 from ._common import LOWP, cast, check, f32c, flow_dtype, payload_dtype, require_gpu
 
 
@@ -157,9 +162,25 @@ def mx_covered(image, taps):
     return image.dtype == torch.float32 and taps.dtype in LOWP and lp_backward_covered(image, taps)
 
 
+def _backward_mx(input1, input2, input3, gradoutput, want1):
+    """_backward_fp32 on the mixed tensors as they are (libmemc_hip_mx_grad.so): the same gradinput1 decision for this
+    shape (so the kernel takes the float32 library's PART for the call); None where the library declines the call
+    (return code 1: nothing was touched)"""
+    gradinput1 = torch.zeros_like(input1) if want1 else None     # (mx_covered: a NULL gradinput1 is served)
+    gradinput2 = torch.empty_like(input2)                # every element is written (invalid sites store zero)
+    gradinput3 = torch.empty_like(input3)
+    err = my_lib_mx_grad.FilterInterpolationLayer_gpu_backward_mx(
+        input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3)
+    if err == 1:
+        return None
+    check(err, "FilterInterpolationLayer_gpu_backward_mx")
+    return gradinput1, gradinput2, gradinput3
+
+
 class _FilterInterpolationMxFunction(Function):
     """a float32 image, float16 / bfloat16 taps, the flow in float32 or the taps' dtype: forward on libmemc_hip_mx.so
-    (where it declines: promoted to float32, the float32 kernel); backward: the promoted call's, on the widened tensors"""
+    (where it declines: promoted to float32, the float32 kernel); backward on libmemc_hip_mx_grad.so (where it declines:
+    the promoted call's, on the widened tensors)"""
 
     @staticmethod
     def forward(ctx, input1, input2, input3):
@@ -178,8 +199,12 @@ class _FilterInterpolationMxFunction(Function):
     @once_differentiable
     def backward(ctx, gradoutput):
         saved = ctx.saved_tensors
-        input1, input2, input3 = (t.float() for t in saved)  # contiguous already
-        grads = _backward_fp32(input1, input2, input3, f32c(gradoutput), ctx.needs_input_grad[0])
+        gradoutput = f32c(gradoutput)
+        grads = _backward_mx(*saved, gradoutput, ctx.needs_input_grad[0])
+        if grads is not None:                                # each gradient in its input's dtype already
+            return grads
+        input1, input2, input3 = (t.float() for t in saved)  # declined, nothing touched: the promoted route
+        grads = _backward_fp32(input1, input2, input3, gradoutput, ctx.needs_input_grad[0])
         return tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, saved))
 
 

@@ -10,7 +10,12 @@ _blend_backward on the widened inputs).  The native route is the code the autogr
 _blend_backward with the half tensors).  Both are timed as whole backward passes, casts and allocations included,
 ALTERNATELY, round after round, so that clock and thermal drift fall on both alike; each launch rotates over input sets
 that together exceed the 256 MiB Infinity Cache several times.  Printed per row: the per-round medians of both routes,
-the median over the rounds, the spread (max - min over the rounds, relative to the median) and the ratio."""
+the median over the rounds, the spread (max - min over the rounds, relative to the median) and the ratio.
+
+The `mixed` group (--only mixed) is the same comparison for the call torch.autocast makes -- a float32 image and a float32
+gradoutput beside half taps: the promoted route (the saved taps and flow cast to float32, _backward_fp32, the tap and flow
+gradients cast back: what _FilterInterpolationMxFunction.backward ran before libmemc_hip_mx_grad.so and still runs where
+that library declines) against the one kernel on the tensors as they are (_backward_mx)."""
 import argparse
 import json
 import math
@@ -31,15 +36,16 @@ from tools import synth                        # noqa: E402
 ROTATE_BYTES = 1 << 30
 
 
-def _sets(shape, n, blend, T, half_flow, seed):
+def _sets(shape, n, blend, T, half_flow, seed, mixed=False):
     B, C, H, W = shape
     ft = T if half_flow else torch.float32
+    it = torch.float32 if mixed else T                        # the image and gradoutput of a mixed call stay float32
     out = []
     for i in range(n):
         t = synth.torch_inputs("cuda", B, C, H, W, flow_kind="smooth", seed=seed + 97 * i)
         g = torch.Generator("cuda").manual_seed(seed + i)
-        s = {"x": t["x"].to(T), "flow": t["flow"].to(ft), "filt": t["filt"].to(T),
-             "gout": torch.randn(B, C, H, W, device="cuda", generator=g).to(T)}
+        s = {"x": t["x"].to(it), "flow": t["flow"].to(ft), "filt": t["filt"].to(T),
+             "gout": torch.randn(B, C, H, W, device="cuda", generator=g).to(it)}
         if blend:
             u = synth.torch_inputs("cuda", B, C, H, W, flow_kind="smooth", seed=seed + 97 * i + 1)
             o = torch.rand(B, 1, H, W, device="cuda", generator=g)
@@ -72,6 +78,19 @@ def _callers(op, sets, want1):
             grads = FL._backward_lp(*saved, s["gout"], want1)
             assert grads is not None, "not covered"
             return tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, saved))
+    elif op == "mx":
+        def widened():                                       # the promoted route
+            s = pick()
+            saved = (s["x"], s["flow"], s["filt"])
+            x, flow, filt = (t.float() for t in saved)
+            grads = FL._backward_fp32(x, flow, filt, s["gout"], want1)
+            return tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, saved))
+
+        def native():
+            s = pick()
+            grads = FL._backward_mx(s["x"], s["flow"], s["filt"], s["gout"], want1)
+            assert grads is not None, "not covered"
+            return grads
     else:
         def _blend(half):
             s = pick()
@@ -91,8 +110,10 @@ def _callers(op, sets, want1):
 def run_case(name, op, shape, T, half_flow, want1, rounds, iters):
     B, C, H, W = shape
     per_set = B * H * W * (2 * C + 16 + 2 * 4) * (2 if op == "blend" else 1) * 2        # half bytes, roughly
+    if op == "mx":
+        per_set = B * H * W * (2 * C * 4 + 16 * 2 + 2 * 4)    # float32 image and gradoutput, half taps
     n = max(2, math.ceil(ROTATE_BYTES / per_set))
-    sets = _sets(shape, n, op == "blend", T, half_flow, seed=2468)
+    sets = _sets(shape, n, op == "blend", T, half_flow, seed=2468, mixed=op == "mx")
     calls = _callers(op, sets, want1)
     times = {"widened": [], "native": []}
     for _ in range(rounds):
@@ -130,6 +151,15 @@ def main():
     cases.append(("fi_bwd bf16 8x3x256x448 fp32 flow noimage", "fi", (8, 3, 256, 448), torch.bfloat16, False, False))
     cases.append(("fi_bwd bf16 8x3x256x448 fp32 flow image", "fi", (8, 3, 256, 448), torch.bfloat16, False, True))
     cases.append(("blend_bwd bf16 32x3x720x1280 fp32 flow", "blend", big, torch.bfloat16, False, True))
+    # the mixed group: float32 image and gradoutput, half taps; the promoted route against libmemc_hip_mx_grad.so
+    for shape in (big, (8, 3, 256, 448)):
+        for tname, T in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
+            for half_flow in (False, True):
+                for want1 in (True, False):
+                    cases.append(("mixed_bwd %s %s %s flow %s" % (tname, "x".join(map(str, shape)),
+                                                                   "T" if half_flow else "fp32",
+                                                                   "image" if want1 else "noimage"),
+                                  "mx", shape, T, half_flow, want1))
     rows = []
     for name, op, shape, T, half_flow, want1 in cases:
         if a.only and a.only not in name:
