@@ -1,0 +1,312 @@
+"""tests/_exact.py -- inputs on which the warps and the projection sums are exact in fp32, whatever the order of the sums.
+
+The grid
+    image        k / 16,  k = 0 .. 15            (2^-4)
+    taps         k / 8,   k = 0 .. 7             (2^-3)
+    occlusion    k / 8,   k = -8 .. 8            (2^-3; a block of zeros and a block of negative values, as np_occlusion)
+    depth        k / 8,   k = 1 .. 9             (2^-3)
+    gradoutput   integers in [-G, G], G = 8
+    flow         round(4 f) / 4 of an existing generator's flow f (2^-2): a quarter of the sites per axis sit on integer
+                 coordinates, so alpha and beta are 0, 1/4, 1/2 or 3/4 and a bilinear weight (1 - alpha)(1 - beta) is a
+                 multiple of 2^-4.  Stored in bf16 the flow is clipped to +-63.75, in fp16 to +-511.75 (the largest
+                 magnitudes those formats hold on the quarter grid); stored in fp32 it is not clipped.
+Every value is a number of fp16 and of bf16.  Image, taps and gradoutput come from a generator seeded apart from the
+flow's (seed + 1000), so that the flow is the very field tests/_lowp_paths.py counts.
+
+The quantum of each result (the power of two every term and every partial sum is a multiple of)
+    adaptive warp (FilterInterpolation), out = sum_taps tap * (bilinear mix of four pixels)
+        forward          pixel 2^-4 * tap 2^-3 * weight 2^-4                        = 2^-11
+        blend forward    the above times an occlusion 2^-3                          = 2^-14
+        image gradient   gradoutput 1 * tap 2^-3 * weight 2^-4                      = 2^-7
+        tap gradient     gradoutput 1 * pixel 2^-4 * weight 2^-4                    = 2^-8
+        flow gradient    gradoutput 1 * tap 2^-3 * pixel 2^-4 * (1 - alpha) 2^-2    = 2^-9
+      the blend's backward works on gradoutput * occlusion (2^-3):
+        tap gradient 2^-11, flow gradient 2^-12; occlusion gradient = sum_c gradoutput * forward = 2^-11
+    bilinear warp (Interpolation, InterpolationCh)
+        forward 2^-4 * 2^-4 = 2^-8, image gradient 1 * 2^-4 = 2^-4, flow gradient 1 * 2^-4 * 2^-2 = 2^-6
+    projection sums
+        flow 2^-2; with a depth 2^-3 * 2^-2 = 2^-5; counts: integers, or multiples of 2^-3 with a depth
+
+Why order cannot matter.  A sum of multiples of 2^-q whose absolute values add up to M has every partial sum, in any
+order and under any grouping, a multiple of 2^-q below M in magnitude: where M * 2^q < 2^24 each of them is a number
+of fp32 and no addition rounds.  A fused multiply-add rounds once where a multiply and an add round twice: where neither
+rounds the two agree.  The packed fixed-point planes, the LDS atomics, the global atomics and the oracle's sequential
+loop therefore all return the same bits.  budget() gives M per output; tests/test_exact_inputs.py asserts
+M * 2^q < 2^24 for every case the GPU module runs and shows with a float64 build of the oracle that nothing rounded.
+
+What such inputs cannot see: a difference in rounding ORDER (a contraction, another association).  The bit-equality
+tests between the libraries stay for that.
+"""
+import os
+import sys
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(_HERE)
+for _p in (ROOT, os.path.join(ROOT, "memc-net_amd"), _HERE):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import _lowp_paths as LP      # noqa: E402
+from tools import synth       # noqa: E402
+
+G = 8                         # |gradoutput| <= G
+
+# log2 of one over the quantum, per output
+Q = dict(fi_fwd=11, blend_fwd=14, fi_image=7, fi_taps=8, fi_flow=9, blend_taps=11, blend_flow=12, blend_occ=11,
+         bl_fwd=8, bl_image=4, bl_flow=6, proj=2, dproj=5)
+LIMIT = 2.0 ** 24
+
+CLIP = {"fp32": None, "fp16": 511.75, "bf16": 63.75}
+
+# the two cases test_gpu_blend_grad.py adds to the census table (the minimum width; a wide row of mostly invalid sites)
+EXTRA = [(2, 37, 8, "smooth", 4.0, 31), (1, 20, 1280, "iid", 0.6 * 1280, 32)]
+# one case of this module's own: Gaussian flows all but never sit exactly on an edge of the validity test, and no case above
+# has five sites on every one of them at once (|fx| == W / 2 needs a narrow image, the valid border sites a gentler flow
+# than 1x40x40-iid30's).  Four 40 x 40 images under an i.i.d. flow of sigma 14: 11 or more sites on each of the six edges.
+EDGES = (4, 40, 40, "iid", 14.0, 61)
+TABLE = LP.CASES + EXTRA + [EDGES]
+TABLE_IDS = LP.CASE_IDS + ["2x37x8-min-width", "1x20x1280-far", "4x40x40-edges"]
+FAR = EXTRA[1]                # keeps its slow and capped sites only unclipped: flow stored in fp32 only
+
+
+def quantise_flow(f, storage="fp32"):
+    """round(4 f) / 4, clipped to what `storage` holds on the quarter grid"""
+    q = np.round(np.asarray(f, dtype=np.float64) * 4.0) / 4.0
+    if CLIP[storage] is not None:
+        q = np.clip(q, -CLIP[storage], CLIP[storage])
+    return np.ascontiguousarray(q, dtype=np.float32)
+
+
+def payload(seed, B, C, H, W, taps=16, g=G):
+    """(image, taps, gradoutput) on the grid, from a generator of its own"""
+    rng = np.random.default_rng(seed + 1000)
+    x = (rng.integers(0, 16, (B, C, H, W)) / 16.0).astype(np.float32)
+    filt = (rng.integers(0, 8, (B, taps, H, W)) / 8.0).astype(np.float32)
+    gout = rng.integers(-g, g + 1, (B, C, H, W)).astype(np.float32)
+    return x, filt, gout
+
+
+def occlusion(seed, B, H, W):
+    """k / 8 in [0, 1] with np_occlusion's block of zeros and block of negative values"""
+    rng = np.random.default_rng(seed + 2000)
+    o = (rng.integers(0, 9, (B, 1, H, W)) / 8.0).astype(np.float32)
+    o[:, :, H // 4:H // 2, W // 4:W // 2] = 0.0
+    o[:, :, H // 2:3 * H // 4, W // 2:3 * W // 4] *= -1.0
+    return o
+
+
+def depth(seed, B, H, W):
+    rng = np.random.default_rng(seed + 3000)
+    return (rng.integers(1, 10, (B, 1, H, W)) / 8.0).astype(np.float32)
+
+
+_CACHE = {}
+
+
+def _once(key, make):
+    if key not in _CACHE:
+        _CACHE[key] = make()
+    return _CACHE[key]
+
+
+def table_flow(case, storage="fp32", second=False):
+    return quantise_flow(LP.case_flow(case, second), storage)
+
+
+def table_inputs(case, C=3, storage="fp32"):
+    """(image, flow, taps, gradoutput) of a table case; never written"""
+    def make():
+        B, H, W, _kind, _sigma, seed = case
+        x, filt, gout = payload(seed, B, C, H, W)
+        return x, table_flow(case, storage), filt, gout
+    return _once(("table", case, C, storage), make)
+
+
+def blend_inputs(case, storage="fp32"):
+    """dict x0, x2, f0, f1, k0, k1, o0, o1, gout of a table case: the second direction's flow is _lowp_paths' (seed + 100)"""
+    def make():
+        B, H, W, _kind, _sigma, seed = case
+        x0, k0, gout = payload(seed, B, 3, H, W)
+        x2, k1, _ = payload(seed + 100, B, 3, H, W)
+        return dict(x0=x0, x2=x2, f0=table_flow(case, storage), f1=table_flow(case, storage, True), k0=k0, k1=k1,
+                    o0=occlusion(seed, B, H, W), o1=occlusion(seed + 100, B, H, W), gout=gout)
+    return _once(("blend", case, storage), make)
+
+
+def shaped_inputs(B, C, H, W, kind, sigma, seed, taps=16):
+    """a case given by its shape (test_gpu_parity.py's tables): the flow is the first draw from default_rng(seed)"""
+    def make():
+        f = synth.np_flow(np.random.default_rng(seed), B, H, W, kind, sigma)
+        x, filt, gout = payload(seed, B, C, H, W, taps)
+        return x, quantise_flow(f), filt, gout
+    return _once(("shape", B, C, H, W, kind, sigma, seed, taps), make)
+
+
+def many_inputs(row):
+    """a row (B, C, H, W, kind) of test_gpu_parity.MANY, quantised; the flow as test_filter_interpolation_backward_many_channels draws it"""
+    def make():
+        import test_gpu_parity as FP32
+        B, C, H, W, kind = row
+        rng = np.random.default_rng(sum(row[:4]))
+        synth.np_image(rng, B, C, H, W), synth.np_filter(rng, B, H, W), synth.np_image(rng, B, C, H, W)    # (its draws before the flow)
+        f = FP32._many_channel_flows(kind, rng, B, H, W)
+        x, filt, gout = payload(sum(row[:4]), B, C, H, W)
+        return x, quantise_flow(f), filt, gout
+    return _once(("many", row), make)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# projection
+# ------------------------------------------------------------------------------------------------------------------
+def project_sums(flow, dep=None):
+    """the scatter of oracle/memc_oracle.c project_scatter in float64, before the division: (s [B, 2, H, W], c [B, 1, H, W])"""
+    B, _, H, W = flow.shape
+    s, c = np.zeros((B, 2, H, W), np.float64), np.zeros((B, 1, H, W), np.float64)
+    fx, fy = flow[:, 0].astype(np.float32), flow[:, 1].astype(np.float32)
+    x2 = np.arange(W, dtype=np.float32)[None, None, :] + fx
+    y2 = np.arange(H, dtype=np.float32)[None, :, None] + fy
+    ok = (x2 >= 0) & (y2 >= 0) & (x2 <= np.float32(W - 1)) & (y2 <= np.float32(H - 1))
+    b, y, x = np.nonzero(ok)
+    L, T = x2[ok].astype(np.int64), y2[ok].astype(np.int64)
+    R, Bm = np.minimum(L + 1, W - 1), np.minimum(T + 1, H - 1)
+    d = np.ones(len(b)) if dep is None else dep[:, 0][ok].astype(np.float64)
+    vx, vy = -d * fx[ok].astype(np.float64), -d * fy[ok].astype(np.float64)
+    for yy, xx in ((T, L), (T, R), (Bm, L), (Bm, R)):           # (R == L or Bm == T: the same cell twice, as the reference)
+        np.add.at(s[:, 0], (b, yy, xx), vx)
+        np.add.at(s[:, 1], (b, yy, xx), vy)
+        np.add.at(c[:, 0], (b, yy, xx), d)
+    return s, c
+
+
+def projection_inputs(name):
+    """(flow, depth) by name: rows 0, 5, 8 of test_gpu_parity.CASES, two pans and a few far sources, all on the grid and
+    no larger than 200 x 320"""
+    def make():
+        if name.startswith("row"):
+            import test_gpu_parity as FP32
+            B, _C, H, W, kind, sigma, seed = FP32.CASES[int(name[3:])]
+            f = synth.np_flow(np.random.default_rng(seed), B, H, W, kind, sigma)
+        elif name.startswith("pan"):
+            px, py, sigma = {"pan216": (216.0, 0.0, 1.0), "pan-300": (-300.0, 0.0, 1.5)}[name]
+            B, H, W = 1, 200, 320
+            f = synth.np_flow(np.random.default_rng(int(abs(px) * 7 + abs(py) * 13 + sigma)), B, H, W, "smooth", sigma)
+            f[0, 0] += px
+            f[0, 1] += py
+            f[0, :, 50:70, 100:140] = 0.0                            # a static patch: far from the pan
+            f[0, 0, 120:130, 280:300] -= 60.0                        # a fast object
+        elif name == "far":                                          # test_projection_with_a_few_far_sources' image 0, smaller
+            B, H, W = 1, 170, 320
+            f = synth.np_flow(np.random.default_rng(4711), B, H, W, "smooth", 4.0)
+            f[0, :, 60:70, 200:230] = 300.0                          # a hole (its sources leave the image) ...
+            for (y, x, fx, fy) in ((5, 7, 150.0, 0.0), (100, 300, -200.5, 40.25), (160, 20, 30.0, -100.0), (64, 210, 0.0, 25.0),
+                                   (40, 180, 35.5, 24.75), (90, 100, -24.0, 3.0), (12, 250, 23.75, -23.75)):
+                f[0, 0, y, x], f[0, 1, y, x] = fx, fy                # ... that (40, 180) -> (215.5, 64.75) lands in
+        else:
+            raise ValueError(name)
+        B, _, H, W = f.shape
+        return quantise_flow(f), depth(len(name), B, H, W)          # (any seed: the depths are k / 8 whatever it is)
+    return _once(("proj", name), make)
+
+
+PROJECTION = ["row0", "row5", "row8", "pan216", "pan-300", "far"]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the proof obligations
+# ------------------------------------------------------------------------------------------------------------------
+def flow_bound(C, g=G, occ=1.0):
+    """sum of absolute terms of a flow gradient: per channel and tap |gradoutput| * tap * (four pixels, two weights that add
+    up to one) <= 2 g even when the kernel expands the pixel differences: 16 taps * 2 = 32 (the mix itself stays below 16)"""
+    return 32.0 * C * g * occ
+
+
+def budget(O, x, flow, filt, gout, occ=None):
+    """M per output of the adaptive warp: the oracle O (fp32 or float64 front-end) on |gradoutput| and the non-negative
+    image and taps, where no term cancels; the flow gradient's analytic bound.  occ: the blend's backward (gradoutput * occ)."""
+    assert x.min() >= 0 and filt.min() >= 0
+    C = x.shape[1]
+    ga = np.abs(gout if occ is None else gout * occ).astype(np.float32)
+    g1, _g2, g3 = O.filter_interpolation_backward(x, flow, filt, ga)
+    fwd = O.filter_interpolation_forward(x, flow, filt)
+    m = dict(fi_fwd=float(fwd.max()), fi_image=float(g1.max()), fi_taps=float(g3.max()), fi_flow=flow_bound(C))
+    if occ is not None:
+        m = dict(blend_fwd=2.0 * float(fwd.max()), blend_taps=m["fi_taps"], blend_flow=m["fi_flow"],
+                 blend_occ=float(C * G * fwd.max()))
+    return m
+
+
+def bilinear_budget(O, x, flow, gout):
+    assert x.min() >= 0
+    g1, _ = O.interpolation_ch_backward(x, flow, np.abs(gout))
+    return dict(bl_fwd=float(O.interpolation_ch_forward(x, flow).max()), bl_image=float(g1.max()),
+                bl_flow=4.0 * x.shape[1] * G)              # per channel |gradoutput| * four pixels below one
+
+
+def holds(m):
+    """M * 2^q < 2^24 for every output of m"""
+    return all(v * 2.0 ** Q[k] < LIMIT for k, v in m.items())
+
+
+def border_sites(flow):
+    """sites exactly on the edges of the validity test: valid ones on x2 == 0, x2 == W - 1, y2 == 0, y2 == H - 1 (the `<=` /
+    `>=` sides) and sites with |fx| == W / 2, |fy| == H / 2 (invalid by the strict `<`)"""
+    B, _, H, W = flow.shape
+    valid, _, _ = LP.locate(flow)
+    fx, fy = flow[:, 0], flow[:, 1]
+    x2 = np.arange(W, dtype=np.float32)[None, None, :] + fx
+    y2 = np.arange(H, dtype=np.float32)[None, :, None] + fy
+    return dict(x2_0=int((valid & (x2 == 0)).sum()), x2_last=int((valid & (x2 == W - 1)).sum()),
+                y2_0=int((valid & (y2 == 0)).sum()), y2_last=int((valid & (y2 == H - 1)).sum()),
+                fx_half=int((np.abs(fx) == W / 2.0).sum()), fy_half=int((np.abs(fy) == H / 2.0).sum()))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the cases tests/test_gpu_exact.py runs and tests/test_exact_inputs.py proves, by name
+# ------------------------------------------------------------------------------------------------------------------
+STORAGES = ["fp32", "fp16", "bf16"]
+# channel counts of the forward per table case, as test_gpu_lowp_paths.FWD_CHANNELS; the three added cases: RGB
+FWD_CHANNELS = [[3, 8, 5, 64], [3, 8, 5, 1], [3, 8, 5, 64], [3, 8, 5], [3, 8, 5], [3, 8, 5], [3], [3], [3]]
+# (B, C, H, W, flow kind, sigma, seed, taps): ragged widths (W % 4 = 2, 1), the minimum width, other filter sizes
+SHAPES = {
+    "W50-C3": (1, 3, 20, 50, "smooth", 3.0, 50, 16), "W50-C8": (1, 8, 20, 50, "smooth", 3.0, 51, 16),
+    "W133-C3": (2, 3, 24, 133, "smooth", 5.0, 52, 16), "W133-C8": (2, 8, 24, 133, "smooth", 5.0, 53, 16),
+    "W4-C3": (2, 3, 24, 4, "smooth", 1.0, 54, 16), "W4-C8": (2, 8, 24, 4, "smooth", 1.0, 55, 16),
+    "fs2": (2, 3, 21, 34, "iid", 3.0, 22, 4), "fs3": (2, 3, 21, 34, "iid", 3.0, 23, 9), "fs6": (2, 3, 21, 34, "iid", 3.0, 26, 36),
+}
+LAYER_CASE = (2, 40, 64, "smooth", 4.0, 41)          # the layers' 2x3x40x64
+
+
+def storages_of(case):
+    return ["fp32"] if case == FAR else STORAGES
+
+
+def parity_blend_cases():
+    """test_gpu_parity.BLEND_CASES as (B, C, H, W, kind, sigma, seed)"""
+    import test_gpu_parity as FP32
+    return FP32.BLEND_CASES
+
+
+def parity_blend_inputs(case):
+    def make():
+        B, C, H, W, kind, sigma, seed = case
+        h = {}
+        for d, (x, f, k, o) in enumerate((("x0", "f0", "k0", "o0"), ("x2", "f1", "k1", "o1"))):
+            h[x], h[f], h[k], _ = shaped_inputs(B, C, H, W, kind, sigma, seed + 100 * d)
+            h[o] = occlusion(seed + 100 * d, B, H, W)
+        h["gout"] = shaped_inputs(B, C, H, W, kind, sigma, seed)[3]
+        return h
+    return _once(("pblend", case), make)
+
+
+def bilinear_rgb_cases():
+    """table cases 0, 2, 5: (id, image, flow, gradoutput)"""
+    for ci in (0, 2, 5):
+        x, flow, _filt, gout = table_inputs(TABLE[ci], 3)
+        yield TABLE_IDS[ci], x, flow, gout
+
+
+def many_rows():
+    import test_gpu_parity as FP32
+    return FP32.MANY
