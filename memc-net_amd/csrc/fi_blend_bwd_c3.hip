@@ -18,11 +18,8 @@
 // Every element of the three outputs is assigned; the results are a pure function of the inputs.
 #include "memc_common.hpp"
 #include "memc_fi_bwd_c3.hpp"
-#include "memc_desc.hpp"
-#include "memc_launch.hpp"
+#include "memc_fi_abi.hpp"
 #include "memc_warp_blend_grad.h"
-
-#include <math.h>
 
 namespace memc {
 
@@ -219,10 +216,9 @@ __global__ __launch_bounds__(NT, 2) void fi_blend_bwd_c3(
 template <int NT = 256>
 static void launch_fi_blend_bwd_c3(const FiBlendBwdCall &k)
 {
-    using G = TileGeom<16, 3072, NT>;
-    const int ntx = (k.w + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH;
-    hipLaunchKernelGGL((fi_blend_bwd_c3<NT>), dim3((unsigned)ntx * nty * k.batch), dim3(NT), PkGeomT<NT>::kLds, k.stream,
-                       k.w, k.h, ntx, nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h,
+    const TileGrid g = fi_tile_grid<TileGeom<16, 3072, NT>>(k.w, k.h);
+    hipLaunchKernelGGL((fi_blend_bwd_c3<NT>), dim3((unsigned)g.ntx * g.nty * k.batch), dim3(NT), PkGeomT<NT>::kLds, k.stream,
+                       k.w, k.h, g.ntx, g.nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h,
                        k.s4.b, k.s4.h, k.in1, k.flow, k.filt, k.occ, k.gout, k.gflow, k.gfilt, k.gocc);
 }
 
@@ -231,19 +227,7 @@ static void launch_fi_blend_bwd_c3(const FiBlendBwdCall &k)
 // ==================================================================================================
 // C ABI (include/memc_warp_blend_grad.h)
 // ==================================================================================================
-namespace {
-
 using namespace memc;
-constexpr int kErr = -1;
-constexpr int kNotCovered = 1;
-
-// occlusion [N, 1, H, W] matching input [N, C, H, W]
-inline bool occlusion_matches(const memc_tensor4 *in1, const memc_tensor4 *occ)
-{
-    return occ->size[0] == in1->size[0] && occ->size[1] == 1 && occ->size[2] == in1->size[2] && occ->size[3] == in1->size[3];
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -259,28 +243,27 @@ int FilterInterpolationBlendLayer_gpu_backward(memc_stream_t stream, const memc_
     for (const memc_tensor4 *t : {input, flow, filter, occlusion, gradoutput, gradflow, gradfilter, gradocclusion})
         if (!ok(t)) return kErr;
     if (!flow_matches(input, flow) || !taps_match(input, filter) || !occlusion_matches(input, occlusion)) return kErr;
-    const int64_t taps = filter->size[1];
-    const int fs = (int)lround(sqrt((double)taps));
-    if (fs < 1 || (int64_t)fs * fs != taps) return kErr;
+    const int fs = fi_filter_side_exact(filter->size[1]);
+    if (fs < 1) return kErr;
     if (!same_layout(input, gradoutput) || !same_layout(flow, gradflow) || !same_layout(filter, gradfilter) ||
         !same_layout(occlusion, gradocclusion))
         return kErr;
-    const int n = (int)input->size[0], c = (int)input->size[1], h = (int)input->size[2], w = (int)input->size[3];
-    if (n == 0 || c == 0 || h == 0 || w == 0) return 0;
+    const FiChecked q = fi_sizes(fs, input);
+    if (q.done) return q.code;
     // coverage: the tiled RGB kernel; anything else is the caller's composition of the warp's entry points
-    if (!(c == 3 && fs == 4 && w % 4 == 0 && w >= 8 &&
-          plane_fits_u32(w, h, {(long)input->stride[2], (long)flow->stride[2], (long)filter->stride[2],
-                                (long)occlusion->stride[2]})))
+    if (!(fi_rgb_tiled_shape(q.c, fs, q.w) &&
+          plane_fits_u32(q.w, q.h, {(long)input->stride[2], (long)flow->stride[2], (long)filter->stride[2],
+                                    (long)occlusion->stride[2]})))
         return kNotCovered;
     const FiBlendBwdCall k = {
-        (hipStream_t)stream, w, h, n, plane(input), plane(flow), plane(filter), plane(occlusion),
+        (hipStream_t)stream, q.w, q.h, q.n, plane(input), plane(flow), plane(filter), plane(occlusion),
         reinterpret_cast<const float *>(input->data), reinterpret_cast<const float *>(flow->data),
         reinterpret_cast<const float *>(filter->data), reinterpret_cast<const float *>(occlusion->data),
         reinterpret_cast<const float *>(gradoutput->data), reinterpret_cast<float *>(gradflow->data),
         reinterpret_cast<float *>(gradfilter->data), reinterpret_cast<float *>(gradocclusion->data)};
     t_blend_grad_path = "fi_blend_bwd:tiled_c3";
     launch_fi_blend_bwd_c3<256>(k);
-    return launch_status() == 0 ? 0 : kErr;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -15,6 +15,28 @@
     constexpr bool kF32 = sizeof(st_t<P>) == 4 && sizeof(st_t<FT>) == 4 && sizeof(st_t<GT>) == 4;
     static_assert(kF32 || !RAG, "half storage: widths that are a multiple of four");
     constexpr unsigned zP = sizeof(st_t<P>), zF = sizeof(st_t<FT>), zG = sizeof(st_t<GT>);      // bytes per element
+    // One site (x + j, y) from global memory, each helper's call spelled once: the fp32 kernel's named function, its half
+    // instantiation where the image is stored as the taps are, else the mixed one (memc_fi.hpp; the image gradient's
+    // atomics read no image: no mixed one).  Macros, so that the text the compiler sees stays what it was.
+#define MEMC_SITE_3WAY(NAME, ...)                                                                                       \
+    do {                                                                                                                \
+        if constexpr (kF32) NAME(__VA_ARGS__);                                                                          \
+        else if constexpr (std::is_same_v<I, P>) NAME##_lp<P, FT, GT>(__VA_ARGS__);                                     \
+        else NAME##_mx<P, FT, GT, I>(__VA_ARGS__);                                                                      \
+    } while (0)
+#define MEMC_SITE_TAPS(j)                                                                                               \
+    MEMC_SITE_3WAY(fi_bwd_site_taps, x + j, y, W, H, in_b, s1c, s1h, flow_b + o2 / zF + j, gin2_b + o2 / zF + j, s2c,   \
+                   filt_b + o3 / zP + j, gin3_b + o3 / zP + j, s3c, gout_b + o1 / zG + j)
+#define MEMC_SITE_SCALAR(j)                                                                                             \
+    MEMC_SITE_3WAY(fi_bwd_site_scalar, x + j, y, W, H, 3, 4, in_b, gin1_b, s1c, s1h, flow_b + o2 / zF + j,              \
+                   gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j, gin3_b + o3 / zP + j, s3c, gout_b + o1 / zG + j)
+#define MEMC_SITE_IMAGE_ATOMICS_ARGS(j)                                                                                 \
+    x + j, y, W, H, gin1_b, s1c, s1h, flow_b + o2 / zF + j, s2c, filt_b + o3 / zP + j, s3c, gout_b + o1 / zG + j
+#define MEMC_SITE_IMAGE_ATOMICS(j)                                                                                      \
+    do {                                                                                                                \
+        if constexpr (kF32) fi_bwd_site_image_atomics(MEMC_SITE_IMAGE_ATOMICS_ARGS(j));                                 \
+        else fi_bwd_site_image_atomics_lp<P, FT, GT>(MEMC_SITE_IMAGE_ATOMICS_ARGS(j));                                  \
+    } while (0)
     constexpr int LX = 16;
     using PG = PkGeomT<NT>;
     using G = TileGeom<LX, PG::kCap, NT>;
@@ -98,12 +120,7 @@
         while (todo) {
             const int j = __ffs(todo) - 1;
             todo &= todo - 1;
-            if constexpr (kF32)
-                fi_bwd_site_image_atomics(x + j, y, W, H, gin1_b, s1c, s1h, flow_b + o2 / 4 + j, s2c,
-                                          filt_b + o3 / 4 + j, s3c, gout_b + o1 / 4 + j);
-            else
-                fi_bwd_site_image_atomics_lp<P, FT, GT>(x + j, y, W, H, gin1_b, s1c, s1h, flow_b + o2 / zF + j, s2c,
-                                                        filt_b + o3 / zP + j, s3c, gout_b + o1 / zG + j);
+            MEMC_SITE_IMAGE_ATOMICS(j);
         }
     };
     auto phase1 = [&](const Region &r, unsigned fast) {
@@ -113,17 +130,7 @@
             while (todo) {
                 const int j = __ffs(todo) - 1;
                 todo &= todo - 1;
-                if constexpr (kF32)
-                    fi_bwd_site_taps(x + j, y, W, H, in_b, s1c, s1h, flow_b + o2 / 4 + j, gin2_b + o2 / 4 + j, s2c,
-                                     filt_b + o3 / 4 + j, gin3_b + o3 / 4 + j, s3c, gout_b + o1 / 4 + j);
-                else if constexpr (std::is_same_v<I, P>)
-                    fi_bwd_site_taps_lp<P, FT, GT>(x + j, y, W, H, in_b, s1c, s1h, flow_b + o2 / zF + j,
-                                                   gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j, gin3_b + o3 / zP + j,
-                                                   s3c, gout_b + o1 / zG + j);
-                else
-                    fi_bwd_site_taps_mx<P, FT, GT, I>(x + j, y, W, H, in_b, s1c, s1h, flow_b + o2 / zF + j,
-                                                      gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j,
-                                                      gin3_b + o3 / zP + j, s3c, gout_b + o1 / zG + j);
+                MEMC_SITE_TAPS(j);
             }
         }
     };
@@ -171,39 +178,16 @@
     while (slow) {                            // rare: redone from global memory with global atomics
         const int j = __ffs(slow) - 1;
         slow &= slow - 1;
-        if constexpr (kF32) {
-            if (PART == 0)
-                fi_bwd_site_scalar(x + j, y, W, H, 3, 4, in_b, gin1_b, s1c, s1h, flow_b + o2 / 4 + j, gin2_b + o2 / 4 + j,
-                                   s2c, filt_b + o3 / 4 + j, gin3_b + o3 / 4 + j, s3c, gout_b + o1 / 4 + j);
-            else if (PART == 1)
-                fi_bwd_site_image_atomics(x + j, y, W, H, gin1_b, s1c, s1h, flow_b + o2 / 4 + j, s2c, filt_b + o3 / 4 + j, s3c,
-                                          gout_b + o1 / 4 + j);
-            else
-                fi_bwd_site_taps(x + j, y, W, H, in_b, s1c, s1h, flow_b + o2 / 4 + j, gin2_b + o2 / 4 + j, s2c,
-                                 filt_b + o3 / 4 + j, gin3_b + o3 / 4 + j, s3c, gout_b + o1 / 4 + j);
-        } else {
-            // PART 0 and PART 2 sum gradinput2 in different orders (fi_bwd_site_scalar vs fi_bwd_site_taps): the half
-            // kernel takes the one the fp32 library takes for the same call
-            static_assert(PART != 1, "half storage: PART 0 or 2");
-            if constexpr (std::is_same_v<I, P>) {
-                if (PART == 0)
-                    fi_bwd_site_scalar_lp<P, FT, GT>(x + j, y, W, H, 3, 4, in_b, gin1_b, s1c, s1h, flow_b + o2 / zF + j,
-                                                     gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j,
-                                                     gin3_b + o3 / zP + j, s3c, gout_b + o1 / zG + j);
-                else
-                    fi_bwd_site_taps_lp<P, FT, GT>(x + j, y, W, H, in_b, s1c, s1h, flow_b + o2 / zF + j,
-                                                   gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j, gin3_b + o3 / zP + j,
-                                                   s3c, gout_b + o1 / zG + j);
-            } else {
-                if (PART == 0)
-                    fi_bwd_site_scalar_mx<P, FT, GT, I>(x + j, y, W, H, 3, 4, in_b, gin1_b, s1c, s1h, flow_b + o2 / zF + j,
-                                                        gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j,
-                                                        gin3_b + o3 / zP + j, s3c, gout_b + o1 / zG + j);
-                else
-                    fi_bwd_site_taps_mx<P, FT, GT, I>(x + j, y, W, H, in_b, s1c, s1h, flow_b + o2 / zF + j,
-                                                      gin2_b + o2 / zF + j, s2c, filt_b + o3 / zP + j,
-                                                      gin3_b + o3 / zP + j, s3c, gout_b + o1 / zG + j);
-            }
-        }
+        // PART 0 and PART 2 sum gradinput2 in different orders (fi_bwd_site_scalar vs fi_bwd_site_taps): the half
+        // kernels take the one the fp32 library takes for the same call
+        static_assert(kF32 || PART != 1, "half storage: PART 0 or 2");
+        if (PART == 0) MEMC_SITE_SCALAR(j);
+        else if (PART == 1) MEMC_SITE_IMAGE_ATOMICS(j);
+        else MEMC_SITE_TAPS(j);
     }
+#undef MEMC_SITE_3WAY
+#undef MEMC_SITE_TAPS
+#undef MEMC_SITE_SCALAR
+#undef MEMC_SITE_IMAGE_ATOMICS_ARGS
+#undef MEMC_SITE_IMAGE_ATOMICS
 }

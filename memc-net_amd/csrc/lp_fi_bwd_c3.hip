@@ -11,11 +11,8 @@
 // sum gradinput2 of sites that no LDS band covers in different orders (fi_bwd_site_scalar vs fi_bwd_site_taps).
 #include "memc_common.hpp"
 #include "memc_fi_bwd_c3.hpp"
-#include "memc_desc.hpp"
-#include "memc_launch.hpp"
+#include "memc_fi_abi.hpp"
 #include "memc_warp_lp_grad.h"
-
-#include <math.h>
 
 namespace memc {
 
@@ -46,51 +43,14 @@ __global__ __launch_bounds__(256, 2) void fi_bwd_c3_lp(
 namespace {
 
 using namespace memc;
-constexpr int kErr = -1;
-constexpr int kNotCovered = 1;
 
 template <class P, class FT, class GT, int PART>
 void launch_fi_bwd_c3_lp(const FiBwdCall<st_t<P>, st_t<FT>, st_t<GT>> &k)
 {
-    using G = TileGeom<16>;
-    const int ntx = (k.w + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH;
-    hipLaunchKernelGGL((fi_bwd_c3_lp<P, FT, GT, PART>), dim3((unsigned)ntx * nty * k.batch), dim3(256), PkGeom::kLds, k.stream,
-                       k.w, k.h, ntx, nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h,
-                       k.in1, k.flow, k.filt, k.gout, k.gin1, k.gin2, k.gin3);
-}
-
-template <class P, class FT, class GT>
-int fi_bwd_lp_launch(hipStream_t stream, int w, int h, int n, const memc_tensor4 *in1, const memc_tensor4 *flow,
-                     const memc_tensor4 *filt, const memc_tensor4 *gout, const memc_tensor4 *gin1, const memc_tensor4 *gin2,
-                     const memc_tensor4 *gin3)
-{
-    const FiBwdCall<st_t<P>, st_t<FT>, st_t<GT>> k = {
-        stream, w, h, 3, n, 4, plane(in1), plane(flow), plane(filt),
-        reinterpret_cast<const st_t<P> *>(in1->data), reinterpret_cast<const st_t<FT> *>(flow->data),
-        reinterpret_cast<const st_t<P> *>(filt->data), reinterpret_cast<const st_t<GT> *>(gout->data),
-        gin1 ? reinterpret_cast<float *>(gin1->data) : nullptr, reinterpret_cast<st_t<FT> *>(gin2->data),
-        reinterpret_cast<st_t<P> *>(gin3->data)};
-    if (k.gin1) {                              // the whole backward (the fp32 launcher's PART 0)
-        t_lp_grad_path = "fi_bwd_lp:tiled_c3";
-        launch_fi_bwd_c3_lp<P, FT, GT, 0>(k);
-    } else {                                   // no image gradient (its PART 2)
-        t_lp_grad_path = "fi_bwd_lp:tiled_c3_noimage";
-        launch_fi_bwd_c3_lp<P, FT, GT, 2>(k);
-    }
-    return launch_status();
-}
-
-// the eight (payload, flow, gradoutput) instantiations
-template <class P>
-int dispatch_lp(memc_dtype flowt, memc_dtype goutt, hipStream_t stream, int w, int h, int n, const memc_tensor4 *in1,
-                const memc_tensor4 *flow, const memc_tensor4 *filt, const memc_tensor4 *gout, const memc_tensor4 *gin1,
-                const memc_tensor4 *gin2, const memc_tensor4 *gin3)
-{
-    if (flowt == MEMC_F32)
-        return goutt == MEMC_F32 ? fi_bwd_lp_launch<P, F32, F32>(stream, w, h, n, in1, flow, filt, gout, gin1, gin2, gin3)
-                                 : fi_bwd_lp_launch<P, F32, P>(stream, w, h, n, in1, flow, filt, gout, gin1, gin2, gin3);
-    return goutt == MEMC_F32 ? fi_bwd_lp_launch<P, P, F32>(stream, w, h, n, in1, flow, filt, gout, gin1, gin2, gin3)
-                             : fi_bwd_lp_launch<P, P, P>(stream, w, h, n, in1, flow, filt, gout, gin1, gin2, gin3);
+    const TileGrid g = fi_tile_grid<TileGeom<16>>(k.w, k.h);
+    hipLaunchKernelGGL((fi_bwd_c3_lp<P, FT, GT, PART>), dim3((unsigned)g.ntx * g.nty * k.batch), dim3(256), PkGeom::kLds,
+                       k.stream, k.w, k.h, g.ntx, g.nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b,
+                       k.s3.c, k.s3.h, k.in1, k.flow, k.filt, k.gout, k.gin1, k.gin2, k.gin3);
 }
 
 }  // namespace
@@ -108,32 +68,26 @@ int FilterInterpolationLayer_gpu_backward_lp(memc_stream_t stream, memc_dtype pa
                                              const memc_tensor4 *gradinput3)
 {
     if (!dtypes_ok(payload, flowt) || !dtypes_ok(payload, goutt)) return kErr;
-    if (!ok(input1) || !ok(input2) || !ok(input3) || !ok(gradoutput) || (gradinput1 && !ok(gradinput1)) ||
-        !ok(gradinput2) || !ok(gradinput3))
-        return kErr;                                                                // my_lib_cuda.c:716-718
-    if (!flow_matches(input1, input2) || !taps_match(input1, input3)) return kErr;  // :685-691
-    const int64_t taps = input3->size[1];
-    const int fs = (int)lround(sqrt((double)taps));                                 // :693-694
-    if (fs < 1 || (int64_t)fs * fs != taps) return kErr;
-    if ((gradinput1 && !same_layout(input1, gradinput1)) || !same_layout(input2, gradinput2) ||
-        !same_layout(input3, gradinput3) || !same_layout(input1, gradoutput))
-        return kErr;                                                                // :719-723
-    const int n = (int)input1->size[0], c = (int)input1->size[1], h = (int)input1->size[2], w = (int)input1->size[3];
-    if (n == 0 || c == 0 || h == 0 || w == 0) return 0;
+    const FiChecked q = fi_bwd_checked(fi_filter_side_exact, input1, input2, input3, gradoutput, gradinput1, gradinput2,
+                                       gradinput3);
+    if (q.done) return q.code;
     // coverage: the tiled RGB kernel on 8-byte half quads; anything else is the caller's (widened) business
-    bool covered = c == 3 && fs == 4 && w % 4 == 0 && w >= 8 &&
-                   plane_fits_u32(w, h, {(long)input1->stride[2], (long)input2->stride[2], (long)input3->stride[2]});
+    bool covered = fi_rgb_tiled_shape(q.c, q.fs, q.w) &&
+                   plane_fits_u32(q.w, q.h, {(long)input1->stride[2], (long)input2->stride[2], (long)input3->stride[2]});
     for (const memc_tensor4 *t : {input1, input3, gradinput3}) covered = covered && quad_ok(t);
     if (flowt == payload) covered = covered && quad_ok(input2) && quad_ok(gradinput2);
     if (goutt == payload) covered = covered && quad_ok(gradoutput);
     if (!covered) return kNotCovered;
-    const hipStream_t s = (hipStream_t)stream;
-    const int r = payload == MEMC_F16
-                      ? dispatch_lp<F16>(flowt, goutt, s, w, h, n, input1, input2, input3, gradoutput, gradinput1, gradinput2,
-                                         gradinput3)
-                      : dispatch_lp<BF16>(flowt, goutt, s, w, h, n, input1, input2, input3, gradoutput, gradinput1, gradinput2,
-                                          gradinput3);
-    return r == 0 ? 0 : kErr;
+    // the eight (payload, flow, gradoutput) instantiations
+    return fi_dispatch(payload, flowt, goutt, [&](auto p, auto ft, auto gt) {
+        using P = decltype(p);
+        using FT = decltype(ft);
+        using GT = decltype(gt);
+        return fi_bwd_launch(fi_bwd_call<P, FT, GT>((hipStream_t)stream, q, input1, input2, input3, gradoutput, gradinput1,
+                                                    gradinput2, gradinput3),
+                             t_lp_grad_path, "fi_bwd_lp:tiled_c3", "fi_bwd_lp:tiled_c3_noimage",
+                             [](const auto &k, auto part) { launch_fi_bwd_c3_lp<P, FT, GT, decltype(part)::value>(k); });
+    });
 }
 
 }  // extern "C"

@@ -11,7 +11,8 @@
 //   fi_blend_lp_tiled<T, FT>        fi_fwd_blend_c3: both directions' streams up front, one box -> stage -> gather round each;
 //   fi_fwd_lp_direct / fi_blend_lp_direct   one lane per site, any filter size, any width, any alignment.
 // The LDS holds fp32 pixel quads (staging widens), so the gather and its arithmetic are the fp32 kernels' own: the site
-// geometry, the gather and the one-site paths from global memory are memc_fi.hpp's, the descriptor checks memc_desc.hpp's.
+// geometry, the gather and the one-site paths from global memory are memc_fi.hpp's, the descriptor checks memc_desc.hpp's,
+// what the satellite libraries' C ABIs share memc_fi_abi.hpp's.
 // The two tiled kernels' bodies (lp_fi_fwd_body.inc, lp_fi_blend_body.inc) are shared with libmemc_hip_mx.so (an fp32
 // image beside half taps).
 #include "memc_common.hpp"
@@ -19,11 +20,8 @@
 #include "memc_fi.hpp"
 #include "memc_lp.hpp"
 #include "memc_lp_fi.hpp"
-#include "memc_desc.hpp"
-#include "memc_launch.hpp"
+#include "memc_fi_abi.hpp"
 #include "memc_warp_lp.h"
-
-#include <math.h>
 
 namespace memc {
 
@@ -110,75 +108,58 @@ __global__ __launch_bounds__(256) void fi_blend_lp_direct(
 namespace {
 
 using namespace memc;
-constexpr int kErr = -1;
 
 template <class T, class FT, bool RGB, bool RAGGED = false>
 void launch_fi_fwd_lp_tiled(const FiFwdCall<st_t<T>, st_t<FT>> &k)
 {
-    using G = TileGeom<16>;
-    const int ntx = (k.w + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH;
-    hipLaunchKernelGGL((fi_fwd_lp_tiled<T, FT, RGB, RAGGED>), dim3((unsigned)ntx * nty * k.batch), dim3(256),
-                       tile_lds_bytes<16>(), k.stream, k.w, k.h, k.channel, ntx, nty, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c,
-                       k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.in1, k.flow, k.filt, k.out);
+    const TileGrid g = fi_tile_grid<TileGeom<16>>(k.w, k.h);
+    hipLaunchKernelGGL((fi_fwd_lp_tiled<T, FT, RGB, RAGGED>), dim3((unsigned)g.ntx * g.nty * k.batch), dim3(256),
+                       tile_lds_bytes<16>(), k.stream, k.w, k.h, k.channel, g.ntx, g.nty, k.s1.b, k.s1.c, k.s1.h, k.s2.b,
+                       k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.in1, k.flow, k.filt, k.out);
 }
 
 template <class T, class FT>
-int fi_fwd_lp_launch(hipStream_t stream, int w, int h, int c, int n, int fs, bool tiled, const memc_tensor4 *in1,
-                     const memc_tensor4 *flow, const memc_tensor4 *filt, const memc_tensor4 *out)
+int fi_fwd_lp_launch(const FiFwdCall<st_t<T>, st_t<FT>> &k, bool tiled)
 {
-    const FiFwdCall<st_t<T>, st_t<FT>> k = {
-        stream, w, h, c, n, fs, plane(in1), plane(flow), plane(filt),
-        reinterpret_cast<const st_t<T> *>(in1->data), reinterpret_cast<const st_t<FT> *>(flow->data),
-        reinterpret_cast<const st_t<T> *>(filt->data), reinterpret_cast<st_t<T> *>(out->data)};
     if (tiled) {
-        if (c == 3) {
+        if (k.channel == 3) {
             t_lp_path = "fi_fwd_lp:tiled_c3";
             launch_fi_fwd_lp_tiled<T, FT, true, false>(k);
         } else {
             t_lp_path = "fi_fwd_lp:tiled_c4n";
-            if (c % 4 == 0) launch_fi_fwd_lp_tiled<T, FT, false, false>(k);
+            if (k.channel % 4 == 0) launch_fi_fwd_lp_tiled<T, FT, false, false>(k);
             else launch_fi_fwd_lp_tiled<T, FT, false, true>(k);
         }
     } else {
-        const int tiles_x = (w + kWave - 1) / kWave, tiles_y = (h + 3) / 4;
+        const int tiles_x = (k.w + kWave - 1) / kWave, tiles_y = (k.h + 3) / 4;
         t_lp_path = "fi_fwd_lp:direct";
-        hipLaunchKernelGGL((fi_fwd_lp_direct<T, FT>), dim3((unsigned)tiles_x * tiles_y * n), dim3(256), 0, stream, w, h, c, fs,
-                           tiles_x, tiles_y, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.in1,
-                           k.flow, k.filt, k.out);
+        hipLaunchKernelGGL((fi_fwd_lp_direct<T, FT>), dim3((unsigned)tiles_x * tiles_y * k.batch), dim3(256), 0, k.stream,
+                           k.w, k.h, k.channel, k.filter_size, tiles_x, tiles_y, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c,
+                           k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.in1, k.flow, k.filt, k.out);
     }
     return launch_status();
 }
 
 template <class T, class FT>
-int fi_blend_lp_launch(hipStream_t stream, int w, int h, int c, int n, int fs, bool tiled, const memc_tensor4 *const (&t)[9])
+int fi_blend_lp_launch(const FiBlendFwdCall<st_t<T>, st_t<FT>> &k, bool tiled)
 {
-    const auto *i0 = reinterpret_cast<const st_t<T> *>(t[0]->data), *i2 = reinterpret_cast<const st_t<T> *>(t[1]->data);
-    const auto *f0 = reinterpret_cast<const st_t<FT> *>(t[2]->data), *f1 = reinterpret_cast<const st_t<FT> *>(t[3]->data);
-    const auto *k0 = reinterpret_cast<const st_t<T> *>(t[4]->data), *k1 = reinterpret_cast<const st_t<T> *>(t[5]->data);
-    const auto *q0 = reinterpret_cast<const st_t<T> *>(t[6]->data), *q1 = reinterpret_cast<const st_t<T> *>(t[7]->data);
-    auto *o = reinterpret_cast<st_t<T> *>(t[8]->data);
-    const Plane s1 = plane(t[0]), s2 = plane(t[2]), s3 = plane(t[4]), so = plane(t[6]);      // (so.c is not used)
     if (tiled) {
-        using G = TileGeom<16>;
-        const int ntx = (w + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;
+        const TileGrid g = fi_tile_grid<TileGeom<16>>(k.w, k.h);
         t_lp_path = "fi_blend_lp:tiled_c3";
-        hipLaunchKernelGGL((fi_blend_lp_tiled<T, FT>), dim3((unsigned)ntx * nty * n), dim3(256), tile_lds_bytes<16>(), stream,
-                           w, h, ntx, nty, s1.b, s1.c, s1.h, s2.b, s2.c, s2.h, s3.b, s3.c, s3.h, so.b, so.h, i0, i2, f0, f1, k0,
-                           k1, q0, q1, o);
+        hipLaunchKernelGGL((fi_blend_lp_tiled<T, FT>), dim3((unsigned)g.ntx * g.nty * k.batch), dim3(256),
+                           tile_lds_bytes<16>(), k.stream, k.w, k.h, g.ntx, g.nty, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c,
+                           k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.so.b, k.so.h, k.in0, k.in2, k.flow0, k.flow1, k.filt0, k.filt1,
+                           k.occ0, k.occ1, k.out);
     } else {
-        const int tiles_x = (w + kWave - 1) / kWave, tiles_y = (h + 3) / 4;
+        const int tiles_x = (k.w + kWave - 1) / kWave, tiles_y = (k.h + 3) / 4;
         t_lp_path = "fi_blend_lp:direct";
-        hipLaunchKernelGGL((fi_blend_lp_direct<T, FT>), dim3((unsigned)tiles_x * tiles_y * n), dim3(256), 0, stream, w, h, c,
-                           fs, tiles_x, tiles_y, s1.b, s1.c, s1.h, s2.b, s2.c, s2.h, s3.b, s3.c, s3.h, so.b, so.h, i0, i2, f0,
-                           f1, k0, k1, q0, q1, o);
+        hipLaunchKernelGGL((fi_blend_lp_direct<T, FT>), dim3((unsigned)tiles_x * tiles_y * k.batch), dim3(256), 0, k.stream,
+                           k.w, k.h, k.channel, k.filter_size, tiles_x, tiles_y, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c,
+                           k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.so.b, k.so.h, k.in0, k.in2, k.flow0, k.flow1, k.filt0, k.filt1,
+                           k.occ0, k.occ1, k.out);
     }
     return launch_status();
 }
-
-// the four (payload, flow) instantiations of a launcher
-#define MEMC_LP_DISPATCH(LAUNCH, ...)                                                                                   \
-    (payload == MEMC_F16 ? (flowt == MEMC_F32 ? LAUNCH<F16, F32>(__VA_ARGS__) : LAUNCH<F16, F16>(__VA_ARGS__))         \
-                         : (flowt == MEMC_F32 ? LAUNCH<BF16, F32>(__VA_ARGS__) : LAUNCH<BF16, BF16>(__VA_ARGS__)))
 
 }  // namespace
 
@@ -195,14 +176,18 @@ int FilterInterpolationLayer_gpu_forward_lp(memc_stream_t stream, memc_dtype pay
     if (!dtypes_ok(payload, flowt)) return kErr;
     if (!ok(input1) || !ok(input2) || !ok(input3) || !ok(output)) return kErr;        // my_lib_cuda.c:641-643
     if (!flow_matches(input1, input2) || !taps_match(input1, input3)) return kErr;    // :611-617
-    const int fs = (int)sqrt((float)input3->size[1]);                                 // :619-620
+    const int fs = fi_filter_side_ref(input3->size[1]);                               // :619-620
     if (fs < 1) return kErr;
     if (!same_layout(input1, output)) return kErr;                                    // :644-645 (+h)
-    const int n = (int)input1->size[0], c = (int)input1->size[1], h = (int)input1->size[2], w = (int)input1->size[3];
-    if (n == 0 || c == 0 || h == 0 || w == 0) return 0;
-    const bool tiled = fs == 4 && w % 4 == 0 && w >= 8 && quad_ok(input1) && quad_ok(input2) && quad_ok(input3) &&
+    const FiChecked q = fi_sizes(fs, input1);
+    if (q.done) return q.code;
+    const bool tiled = fs == 4 && q.w % 4 == 0 && q.w >= 8 && quad_ok(input1) && quad_ok(input2) && quad_ok(input3) &&
                        quad_ok(output);
-    return MEMC_LP_DISPATCH(fi_fwd_lp_launch, (hipStream_t)stream, w, h, c, n, fs, tiled, input1, input2, input3, output);
+    return fi_dispatch(payload, flowt, [&](auto t, auto ft) {
+        using T = decltype(t);
+        using FT = decltype(ft);
+        return fi_fwd_lp_launch<T, FT>(fi_fwd_call<T, FT>((hipStream_t)stream, q, input1, input2, input3, output), tiled);
+    });
 }
 
 int FilterInterpolationBlendLayer_gpu_forward_lp(memc_stream_t stream, memc_dtype payload, memc_dtype flowt,
@@ -214,22 +199,15 @@ int FilterInterpolationBlendLayer_gpu_forward_lp(memc_stream_t stream, memc_dtyp
 {
     if (!dtypes_ok(payload, flowt)) return kErr;
     const memc_tensor4 *const all[9] = {input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1, output};
-    for (const memc_tensor4 *t : all)
-        if (!ok(t)) return kErr;
-    if (!flow_matches(input0, flow0) || !taps_match(input0, filter0)) return kErr;
-    if (!same_layout(input0, input2) || !same_layout(input0, output) || !same_layout(flow0, flow1) ||
-        !same_layout(filter0, filter1) || !same_layout(occlusion0, occlusion1))
-        return kErr;
-    if (occlusion0->size[0] != input0->size[0] || occlusion0->size[1] != 1 || occlusion0->size[2] != input0->size[2] ||
-        occlusion0->size[3] != input0->size[3])
-        return kErr;
-    const int fs = (int)sqrt((float)filter0->size[1]);
-    if (fs < 1) return kErr;
-    const int n = (int)input0->size[0], c = (int)input0->size[1], h = (int)input0->size[2], w = (int)input0->size[3];
-    if (n == 0 || c == 0 || h == 0 || w == 0) return 0;
-    bool tiled = fs == 4 && c == 3 && w % 4 == 0 && w >= 8;
+    const FiChecked q = fi_blend_fwd_checked(fi_filter_side_ref, all);
+    if (q.done) return q.code;
+    bool tiled = fi_rgb_tiled_shape(q.c, q.fs, q.w);
     for (const memc_tensor4 *t : all) tiled = tiled && quad_ok(t);
-    return MEMC_LP_DISPATCH(fi_blend_lp_launch, (hipStream_t)stream, w, h, c, n, fs, tiled, all);
+    return fi_dispatch(payload, flowt, [&](auto t, auto ft) {
+        using T = decltype(t);
+        using FT = decltype(ft);
+        return fi_blend_lp_launch<T, FT>(fi_blend_fwd_call<T, FT>((hipStream_t)stream, q, all), tiled);
+    });
 }
 
 }  // extern "C"

@@ -2,7 +2,8 @@
 // kernels take them, and one call descriptor per operator family, filled once at the top of an entry point.  The launch
 // function of a kernel family -- tile count, grid, LDS bytes and the argument list, spelled once -- is a function template
 // beside the kernel (launch_fi_fwd_tiled_fs4 in filter_interpolation.hip, ...).  The descriptors are templates over the
-// tensors' storage: float in the fp32 library, st_t<...> (memc_lp.hpp) in the half-precision ones.
+// tensors' storage: float in the fp32 library, st_t<...> (memc_lp.hpp) in the half-precision and mixed ones, which fill
+// them from the memc_tensor4s with memc_fi_abi.hpp's fi_fwd_call / fi_blend_fwd_call / fi_bwd_call.
 #pragma once
 
 #include "memc_warp_lp.h"                      // memc_tensor4
@@ -29,6 +30,16 @@ struct FiFwdCall {
     int w, h, channel, batch, filter_size;
     Plane s1, s2, s3;
     const IT *in1;  const FT *flow;  const T *filt;  IT *out;
+};
+
+// The fused dual warp + occlusion blend forward.  s1: the images and the output; s2: the flows; s3: the taps; so: the
+// occlusions (so.c is not used).  IT as above.
+template <class T = float, class FT = T, class IT = T>
+struct FiBlendFwdCall {
+    hipStream_t stream;
+    int w, h, channel, batch, filter_size;
+    Plane s1, s2, s3, so;
+    const IT *in0, *in2;  const FT *flow0, *flow1;  const T *filt0, *filt1, *occ0, *occ1;  IT *out;
 };
 
 // FilterInterpolation backward.  s1: input1, gradoutput and gradinput1 (always fp32: the tiles' flushes add into it; NULL:

@@ -16,11 +16,8 @@
 #include "memc_fi.hpp"
 #include "memc_lp.hpp"
 #include "memc_lp_fi.hpp"
-#include "memc_desc.hpp"
-#include "memc_launch.hpp"
+#include "memc_fi_abi.hpp"
 #include "memc_warp_mx.h"
-
-#include <math.h>
 
 namespace memc {
 
@@ -52,34 +49,23 @@ __global__ __launch_bounds__(256, 2) void fi_blend_mx_tiled(
 #include "lp_fi_blend_body.inc"
 }
 
-// The fused blend's call.  s1: the images and the output; s2: the flows; s3: the taps; so: the occlusions (so.c is not used).
-template <class T, class FT>
-struct FiBlendMxCall {
-    hipStream_t stream;
-    int w, h, batch;
-    Plane s1, s2, s3, so;
-    const float *in0, *in2;  const FT *flow0, *flow1;  const T *filt0, *filt1, *occ0, *occ1;  float *out;
-};
-
 // The tiles cover the width's quads: 64 x 16 sites each.
 template <class T, class FT>
 void launch_fi_fwd_mx_tiled(const FiFwdCall<st_t<T>, st_t<FT>, float> &k)
 {
-    using G = TileGeom<16>;
-    const int ntx = (k.w + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH;
-    hipLaunchKernelGGL((fi_fwd_mx_tiled<T, FT>), dim3((unsigned)ntx * nty * k.batch), dim3(256), tile_lds_bytes<16>(),
-                       k.stream, k.w, k.h, ntx, nty, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h,
-                       k.in1, k.flow, k.filt, k.out);
+    const TileGrid g = fi_tile_grid<TileGeom<16>>(k.w, k.h);
+    hipLaunchKernelGGL((fi_fwd_mx_tiled<T, FT>), dim3((unsigned)g.ntx * g.nty * k.batch), dim3(256), tile_lds_bytes<16>(),
+                       k.stream, k.w, k.h, g.ntx, g.nty, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c,
+                       k.s3.h, k.in1, k.flow, k.filt, k.out);
 }
 
 template <class T, class FT>
-void launch_fi_blend_mx_tiled(const FiBlendMxCall<st_t<T>, st_t<FT>> &k)
+void launch_fi_blend_mx_tiled(const FiBlendFwdCall<st_t<T>, st_t<FT>, float> &k)
 {
-    using G = TileGeom<16>;
-    const int ntx = (k.w + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH;
-    hipLaunchKernelGGL((fi_blend_mx_tiled<T, FT>), dim3((unsigned)ntx * nty * k.batch), dim3(256), tile_lds_bytes<16>(),
-                       k.stream, k.w, k.h, ntx, nty, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h,
-                       k.so.b, k.so.h, k.in0, k.in2, k.flow0, k.flow1, k.filt0, k.filt1, k.occ0, k.occ1, k.out);
+    const TileGrid g = fi_tile_grid<TileGeom<16>>(k.w, k.h);
+    hipLaunchKernelGGL((fi_blend_mx_tiled<T, FT>), dim3((unsigned)g.ntx * g.nty * k.batch), dim3(256), tile_lds_bytes<16>(),
+                       k.stream, k.w, k.h, g.ntx, g.nty, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c,
+                       k.s3.h, k.so.b, k.so.h, k.in0, k.in2, k.flow0, k.flow1, k.filt0, k.filt1, k.occ0, k.occ1, k.out);
 }
 
 }  // namespace memc
@@ -90,41 +76,6 @@ void launch_fi_blend_mx_tiled(const FiBlendMxCall<st_t<T>, st_t<FT>> &k)
 namespace {
 
 using namespace memc;
-constexpr int kErr = -1;
-constexpr int kNotCovered = 1;
-
-template <class T, class FT>
-int fi_fwd_mx_launch(hipStream_t stream, int w, int h, int n, const memc_tensor4 *in1, const memc_tensor4 *flow,
-                     const memc_tensor4 *filt, const memc_tensor4 *out)
-{
-    const FiFwdCall<st_t<T>, st_t<FT>, float> k = {
-        stream, w, h, 3, n, 4, plane(in1), plane(flow), plane(filt),
-        reinterpret_cast<const float *>(in1->data), reinterpret_cast<const st_t<FT> *>(flow->data),
-        reinterpret_cast<const st_t<T> *>(filt->data), reinterpret_cast<float *>(out->data)};
-    t_mx_path = "fi_fwd_mx:tiled_c3";
-    launch_fi_fwd_mx_tiled<T, FT>(k);
-    return launch_status();
-}
-
-template <class T, class FT>
-int fi_blend_mx_launch(hipStream_t stream, int w, int h, int n, const memc_tensor4 *const (&t)[9])
-{
-    const FiBlendMxCall<st_t<T>, st_t<FT>> k = {
-        stream, w, h, n, plane(t[0]), plane(t[2]), plane(t[4]), plane(t[6]),
-        reinterpret_cast<const float *>(t[0]->data), reinterpret_cast<const float *>(t[1]->data),
-        reinterpret_cast<const st_t<FT> *>(t[2]->data), reinterpret_cast<const st_t<FT> *>(t[3]->data),
-        reinterpret_cast<const st_t<T> *>(t[4]->data), reinterpret_cast<const st_t<T> *>(t[5]->data),
-        reinterpret_cast<const st_t<T> *>(t[6]->data), reinterpret_cast<const st_t<T> *>(t[7]->data),
-        reinterpret_cast<float *>(t[8]->data)};
-    t_mx_path = "fi_blend_mx:tiled_c3";
-    launch_fi_blend_mx_tiled<T, FT>(k);
-    return launch_status();
-}
-
-// the four (taps, flow) instantiations of a launcher
-#define MEMC_MX_DISPATCH(LAUNCH, ...)                                                                                   \
-    (tapt == MEMC_F16 ? (flowt == MEMC_F32 ? LAUNCH<F16, F32>(__VA_ARGS__) : LAUNCH<F16, F16>(__VA_ARGS__))             \
-                      : (flowt == MEMC_F32 ? LAUNCH<BF16, F32>(__VA_ARGS__) : LAUNCH<BF16, BF16>(__VA_ARGS__)))
 
 // fp32 tensors need dword alignment only (f32x4u); a T tensor -- the taps, the occlusions, a flow in T -- 8-byte quads
 inline bool flow_quad_ok(memc_dtype flowt, const memc_tensor4 *flow) { return flowt == MEMC_F32 || quad_ok(flow); }
@@ -144,18 +95,22 @@ int FilterInterpolationLayer_gpu_forward_mx(memc_stream_t stream, memc_dtype tap
     if (!dtypes_ok(tapt, flowt)) return kErr;
     if (!ok(input1) || !ok(input2) || !ok(input3) || !ok(output)) return kErr;
     if (!flow_matches(input1, input2) || !taps_match(input1, input3)) return kErr;
-    const int64_t taps = input3->size[1];
-    const int fs = (int)lround(sqrt((double)taps));
-    if (fs < 1 || (int64_t)fs * fs != taps) return kErr;
+    const int fs = fi_filter_side_exact(input3->size[1]);
+    if (fs < 1) return kErr;
     if (!same_layout(input1, output)) return kErr;
-    const int n = (int)input1->size[0], c = (int)input1->size[1], h = (int)input1->size[2], w = (int)input1->size[3];
-    if (n == 0 || c == 0 || h == 0 || w == 0) return 0;
+    const FiChecked q = fi_sizes(fs, input1);
+    if (q.done) return q.code;
     // coverage: the tiled RGB kernel; anything else is the caller's (promoted) business
-    if (!(c == 3 && fs == 4 && w % 4 == 0 && w >= 8 &&
-          plane_fits_u32(w, h, {(long)input1->stride[2], (long)input2->stride[2], (long)input3->stride[2]}) &&
+    if (!(fi_rgb_tiled_shape(q.c, fs, q.w) &&
+          plane_fits_u32(q.w, q.h, {(long)input1->stride[2], (long)input2->stride[2], (long)input3->stride[2]}) &&
           quad_ok(input3) && flow_quad_ok(flowt, input2)))
         return kNotCovered;
-    return MEMC_MX_DISPATCH(fi_fwd_mx_launch, (hipStream_t)stream, w, h, n, input1, input2, input3, output) == 0 ? 0 : kErr;
+    return fi_dispatch(tapt, flowt, [&](auto t, auto ft) {
+        t_mx_path = "fi_fwd_mx:tiled_c3";
+        launch_fi_fwd_mx_tiled<decltype(t), decltype(ft)>(
+            fi_fwd_call<decltype(t), decltype(ft), F32>((hipStream_t)stream, q, input1, input2, input3, output));
+        return launch_status();
+    });
 }
 
 int FilterInterpolationBlendLayer_gpu_forward_mx(memc_stream_t stream, memc_dtype tapt, memc_dtype flowt,
@@ -167,27 +122,20 @@ int FilterInterpolationBlendLayer_gpu_forward_mx(memc_stream_t stream, memc_dtyp
 {
     if (!dtypes_ok(tapt, flowt)) return kErr;
     const memc_tensor4 *const all[9] = {input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1, output};
-    for (const memc_tensor4 *t : all)
-        if (!ok(t)) return kErr;
-    if (!flow_matches(input0, flow0) || !taps_match(input0, filter0)) return kErr;
-    if (!same_layout(input0, input2) || !same_layout(input0, output) || !same_layout(flow0, flow1) ||
-        !same_layout(filter0, filter1) || !same_layout(occlusion0, occlusion1))
-        return kErr;
-    if (occlusion0->size[0] != input0->size[0] || occlusion0->size[1] != 1 || occlusion0->size[2] != input0->size[2] ||
-        occlusion0->size[3] != input0->size[3])
-        return kErr;
-    const int64_t taps = filter0->size[1];
-    const int fs = (int)lround(sqrt((double)taps));
-    if (fs < 1 || (int64_t)fs * fs != taps) return kErr;
-    const int n = (int)input0->size[0], c = (int)input0->size[1], h = (int)input0->size[2], w = (int)input0->size[3];
-    if (n == 0 || c == 0 || h == 0 || w == 0) return 0;
-    bool covered = c == 3 && fs == 4 && w % 4 == 0 && w >= 8 &&
-                   plane_fits_u32(w, h, {(long)input0->stride[2], (long)flow0->stride[2], (long)filter0->stride[2],
-                                         (long)occlusion0->stride[2]});
+    const FiChecked q = fi_blend_fwd_checked(fi_filter_side_exact, all);
+    if (q.done) return q.code;
+    bool covered = fi_rgb_tiled_shape(q.c, q.fs, q.w) &&
+                   plane_fits_u32(q.w, q.h, {(long)input0->stride[2], (long)flow0->stride[2], (long)filter0->stride[2],
+                                             (long)occlusion0->stride[2]});
     for (const memc_tensor4 *t : {filter0, filter1, occlusion0, occlusion1}) covered = covered && quad_ok(t);
     covered = covered && flow_quad_ok(flowt, flow0) && flow_quad_ok(flowt, flow1);
     if (!covered) return kNotCovered;
-    return MEMC_MX_DISPATCH(fi_blend_mx_launch, (hipStream_t)stream, w, h, n, all) == 0 ? 0 : kErr;
+    return fi_dispatch(tapt, flowt, [&](auto t, auto ft) {
+        t_mx_path = "fi_blend_mx:tiled_c3";
+        launch_fi_blend_mx_tiled<decltype(t), decltype(ft)>(
+            fi_blend_fwd_call<decltype(t), decltype(ft), F32>((hipStream_t)stream, q, all));
+        return launch_status();
+    });
 }
 
 }  // extern "C"
