@@ -1406,109 +1406,99 @@ constexpr bool g_bwd_cn_allow_c3 = false;
 #endif
 bool fi_bwd_cn_class(int channel, int filter_size) { return filter_size == 4 && (channel >= 4 || (g_bwd_cn_allow_c3 && channel == 3)); }
 
-int fi_bwd_cn_launch(hipStream_t stream, int w, int h, int channel, int batch,
-                     int s1b, int s1c, int s1h, int s2b, int s2c, int s2h, int s3b, int s3c, int s3h,
-                     const float *input1, const float *input2, const float *input3, const float *gradoutput,
-                     float *gradinput1, float *gradinput2, float *gradinput3, bool force_direct)
+// Can the owner kernels take this call (FiBwdCall<> or BlBwdCall; row_strides: of every tensor it reads)?  Not a plane
+// beyond 4 GiB, fewer than two whole quads in a row, 4-plane offsets of the owner beyond 32 bits, more tiles than a packed
+// tile index holds -- nor when the measurement arm asks for the direct kernel.
+template <class Call>
+static bool bwd_cn_owner_ok(const Call &k, std::initializer_list<long> row_strides, bool force_direct)
 {
-    if (!fi_bwd_cn_class(channel, 4)) return 0;
+    return !force_direct && plane_fits_u32(k.w, k.h, row_strides) && (k.w & ~3) >= 8 &&
+           4LL * (3LL * k.s1.c + (long long)(k.h - 1) * k.s1.h + k.w) < (1LL << 32) &&
+           (k.w + 63) / 64 <= 0xfff && (k.h + 15) / 16 <= 0x7fff;
+}
+
+// Not taken: gradinput1 is cleared before the caller falls back to the accumulating direct kernel.  0 or -1.
+template <class Call>
+static int bwd_cn_decline(const Call &k)
+{
+    hipLaunchKernelGGL(fi_bwd_zero_rows, dim3((unsigned)k.batch * k.channel * k.h), dim3(256), 0, k.stream, k.gin1, k.w, k.h,
+                       k.channel, k.s1.b, k.s1.c, k.s1.h);
+    return launch_status() == 0 ? 0 : -1;
+}
+
+// a ragged width's cells that no owner stores: cleared before anything adds to them
+template <class Call>
+static void launch_bwd_cn_zero_tail(const Call &k)
+{
+    hipLaunchKernelGGL(bwd_cn_zero_tail, dim3((unsigned)(((int64_t)k.batch * k.channel * k.h + 255) / 256)), dim3(256), 0,
+                       k.stream, k.gin1, k.w & ~3, k.w, k.h, k.channel, k.batch, k.s1.b, k.s1.c, k.s1.h);
+}
+
+// s3 / filt: the taps (the bilinear warp: none); one workgroup per 64 x TH tile
+template <class Fp, int TH, bool TR, class Call>
+static void launch_fi_bwd_image_owner(const Call &k, const Plane &s3, const float *filt, BBox *tbox, unsigned long long *trace)
+{
+    using Gm = OwnGeom<Fp, TH>;
+    allow_big_lds(fi_bwd_image_owner<Fp, TH, TR>, Gm::kBytes);   // per launch: the attribute belongs to the CURRENT device
+    const int ntx = (k.w + 63) / 64, nty = (k.h + 15) / 16, cty = (k.h + TH - 1) / TH;
+    hipLaunchKernelGGL((fi_bwd_image_owner<Fp, TH, TR>), dim3((unsigned)ntx * cty * k.batch), dim3(Gm::kThreads), Gm::kBytes,
+                       k.stream, k.w, k.h, k.w & ~3, k.channel, ntx, cty, nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c,
+                       k.s2.h, s3.b, s3.c, s3.h, k.flow, filt, k.gout, k.gin1, tbox, trace);
+}
+
+int fi_bwd_cn_launch(const FiBwdCall<> &k, bool force_direct)
+{
+    if (!fi_bwd_cn_class(k.channel, 4)) return 0;
+    const int w = k.w, h = k.h, wq = w & ~3;               // the whole quads of a row (round 6: ragged widths, see the top)
     const int ntx = (w + 63) / 64, nty = (h + 15) / 16;
-    const unsigned ntiles = (unsigned)ntx * nty * batch;
-    const int wq = w & ~3;                                 // the whole quads of a row (round 6: ragged widths, see the top)
+    const unsigned ntiles = (unsigned)ntx * nty * k.batch;
     CallScratch scratch;                                   // the site tiles' target boxes
-    if (force_direct || !plane_fits_u32(w, h, {s1h, s2h, s3h}) || wq < 8 ||
-        4LL * (3LL * s1c + (long long)(h - 1) * s1h + w) >= (1LL << 32) ||           // the owner's 4-plane offsets
-        ntx > 0xfff || nty > 0x7fff ||
-        !scratch.alloc((size_t)ntiles * 4 * sizeof(BBox), stream)) {                 // e.g. inside a stream capture
-        hipLaunchKernelGGL(fi_bwd_zero_rows, dim3((unsigned)batch * channel * h), dim3(256), 0, stream, gradinput1, w, h,
-                           channel, (int64_t)s1b, (int64_t)s1c, s1h);
-        return launch_status() == 0 ? 0 : -1;
-    }
+    if (!bwd_cn_owner_ok(k, {k.s1.h, k.s2.h, k.s3.h}, force_direct) ||
+        !scratch.alloc((size_t)ntiles * 4 * sizeof(BBox), k.stream))                 // e.g. inside a stream capture
+        return bwd_cn_decline(k);
     BBox *tbox = static_cast<BBox *>(scratch.p);
-    const bool rag = wq < w;
-    const unsigned tail_rows = (unsigned)(((int64_t)batch * channel * h + 255) / 256);
-    const unsigned tail_sites = (unsigned)(((int64_t)batch * h * (w - wq) + 3) / 4);     // one wave per site, four per workgroup
-    if (rag)                                               // the cells no owner stores: cleared before anything adds to them
-        hipLaunchKernelGGL(bwd_cn_zero_tail, dim3(tail_rows), dim3(256), 0, stream, gradinput1, wq, w, h, channel, batch,
-                           (int64_t)s1b, (int64_t)s1c, s1h);
-#define MEMC_TAPS(RAG_)                                                                                            \
-    hipLaunchKernelGGL(fi_bwd_taps_c4n<RAG_>, dim3(ntiles), dim3(256), tile_lds_bytes<16>() + 64, stream,          \
-                       w, h, wq, channel, ntx, nty, batch, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, \
-                       (int64_t)s3b, (int64_t)s3c, s3h, input1, input2, input3, gradoutput, gradinput1, gradinput2,  \
-                       gradinput3, tbox)
-    if (rag) MEMC_TAPS(true);
-    else MEMC_TAPS(false);
-#undef MEMC_TAPS
-#define MEMC_OWNER(TH, TR, TRACE)                                                                                  \
-    do {                                                                                                           \
-        using Gm_ = OwnGeom<FpFilter, TH>;                                                                         \
-        allow_big_lds(fi_bwd_image_owner<FpFilter, TH, TR>, Gm_::kBytes);   /* per launch: a per-DEVICE attribute */ \
-        const int cty = (h + TH - 1) / TH;                                                                         \
-        hipLaunchKernelGGL((fi_bwd_image_owner<FpFilter, TH, TR>), dim3((unsigned)ntx * cty * batch),              \
-                           dim3(Gm_::kThreads), Gm_::kBytes, stream, w, h, wq, channel, ntx, cty, nty,             \
-                           batch, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b,  \
-                           (int64_t)s3c, s3h, input2, input3, gradoutput, gradinput1, tbox, TRACE);                \
-    } while (0)
+    if (wq < w) launch_bwd_cn_zero_tail(k);
+    const auto taps = wq < w ? fi_bwd_taps_c4n<true> : fi_bwd_taps_c4n<false>;
+    hipLaunchKernelGGL(taps, dim3(ntiles), dim3(256), tile_lds_bytes<16>() + 64, k.stream, w, h, wq, k.channel, ntx, nty, k.batch,
+                       k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.in1, k.flow, k.filt, k.gout,
+                       k.gin1, k.gin2, k.gin3, tbox);
 #ifdef MEMC_MEASURE
-    if (g_trace_cn) MEMC_OWNER(16, true, g_trace_cn);
+    if (g_trace_cn) launch_fi_bwd_image_owner<FpFilter, 16, true>(k, k.s3, k.filt, tbox, g_trace_cn);
     else
 #endif
-        MEMC_OWNER(16, false, nullptr);
-#undef MEMC_OWNER
-    if (rag)
-        hipLaunchKernelGGL(fi_bwd_tail_sites, dim3(tail_sites), dim3(256), 0, stream, w, h, wq, channel, batch, (int64_t)s1b,
-                           (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, (int64_t)s3b, (int64_t)s3c, s3h, input1, input2,
-                           input3, gradoutput, gradinput1, gradinput2, gradinput3);
-    hipLaunchKernelGGL(fi_bwd_far_sites, dim3(ntiles), dim3(256), 0, stream,
-                       w, h, wq, channel, ntx, nty, batch, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h,
-                       (int64_t)s3b, (int64_t)s3c, s3h, input2, input3, gradoutput, gradinput1, tbox);
+        launch_fi_bwd_image_owner<FpFilter, 16, false>(k, k.s3, k.filt, tbox, nullptr);
+    if (wq < w)                                            // one wave per site, four per workgroup
+        hipLaunchKernelGGL(fi_bwd_tail_sites, dim3((unsigned)(((int64_t)k.batch * h * (w - wq) + 3) / 4)), dim3(256), 0, k.stream,
+                           w, h, wq, k.channel, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h,
+                           k.in1, k.flow, k.filt, k.gout, k.gin1, k.gin2, k.gin3);
+    hipLaunchKernelGGL(fi_bwd_far_sites, dim3(ntiles), dim3(256), 0, k.stream, w, h, wq, k.channel, ntx, nty, k.batch, k.s1.b,
+                       k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.flow, k.filt, k.gout, k.gin1, tbox);
     return launch_status() == 0 ? 1 : -1;
 }
 
 // The bilinear warp's backward for the same class of channel counts (C >= 4); same return convention.
-int bl_bwd_cn_launch(hipStream_t stream, int w, int h, int channel, int batch,
-                     int s1b, int s1c, int s1h, int s2b, int s2c, int s2h,
-                     const float *input1, const float *input2, const float *gradoutput,
-                     float *gradinput1, float *gradinput2, bool force_direct)
+int bl_bwd_cn_launch(const BlBwdCall &k, bool force_direct)
 {
-    if (!fi_bwd_cn_class(channel, 4)) return 0;
+    if (!fi_bwd_cn_class(k.channel, 4)) return 0;
+    const int w = k.w, h = k.h, wq = w & ~3;
     const int ntx = (w + 63) / 64, nty = (h + 15) / 16;
-    const unsigned ntiles = (unsigned)ntx * nty * batch;
-    const int wq = w & ~3;
+    const unsigned ntiles = (unsigned)ntx * nty * k.batch;
     CallScratch scratch;                                   // the site tiles' target boxes
-    if (force_direct || !plane_fits_u32(w, h, {s1h, s2h}) || wq < 8 ||
-        4LL * (3LL * s1c + (long long)(h - 1) * s1h + w) >= (1LL << 32) || ntx > 0xfff || nty > 0x7fff ||
-        !scratch.alloc((size_t)ntiles * 4 * sizeof(BBox), stream)) {
-        hipLaunchKernelGGL(fi_bwd_zero_rows, dim3((unsigned)batch * channel * h), dim3(256), 0, stream, gradinput1, w, h,
-                           channel, (int64_t)s1b, (int64_t)s1c, s1h);
-        return launch_status() == 0 ? 0 : -1;
-    }
+    if (!bwd_cn_owner_ok(k, {k.s1.h, k.s2.h}, force_direct) || !scratch.alloc((size_t)ntiles * 4 * sizeof(BBox), k.stream))
+        return bwd_cn_decline(k);
     BBox *tbox = static_cast<BBox *>(scratch.p);
-    const bool rag = wq < w;
     constexpr int kCap = 2496;                             // the forward's staging budget: 39 KiB, 2 x 2 footprint
-    if (rag)
-        hipLaunchKernelGGL(bwd_cn_zero_tail, dim3((unsigned)(((int64_t)batch * channel * h + 255) / 256)), dim3(256), 0, stream,
-                           gradinput1, wq, w, h, channel, batch, (int64_t)s1b, (int64_t)s1c, s1h);
-#define MEMC_FLOW(RAG_)                                                                                            \
-    hipLaunchKernelGGL((bl_bwd_flow_c4n<kCap, RAG_>), dim3(ntiles), dim3(256), (tile_lds_bytes<16, kCap>() + 64), stream,  \
-                       w, h, wq, channel, ntx, nty, batch, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, \
-                       input1, input2, gradoutput, gradinput2, tbox)
-    if (rag) MEMC_FLOW(true);
-    else MEMC_FLOW(false);
-#undef MEMC_FLOW
-    using Gm = OwnGeom<FpBilinear, 16>;
-    allow_big_lds(fi_bwd_image_owner<FpBilinear, 16, false>, Gm::kBytes);   // per launch: the attribute belongs to the current device
-    hipLaunchKernelGGL((fi_bwd_image_owner<FpBilinear, 16, false>), dim3(ntiles), dim3(Gm::kThreads), Gm::kBytes, stream,
-                       w, h, wq, channel, ntx, nty, nty, batch, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c,
-                       s2h, (int64_t)0, (int64_t)0, 0, input2, static_cast<const float *>(nullptr), gradoutput,
-                       gradinput1, tbox, static_cast<unsigned long long *>(nullptr));
-    if (rag)
-        hipLaunchKernelGGL(bl_bwd_tail_sites, dim3((unsigned)(((int64_t)batch * h * (w - wq) + 3) / 4)), dim3(256), 0, stream,
-                           w, h, wq, channel, batch, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h, input1,
-                           input2, gradoutput, gradinput1, gradinput2);
-    hipLaunchKernelGGL(bl_bwd_far_sites, dim3(ntiles), dim3(256), 0, stream,
-                       w, h, wq, channel, ntx, nty, batch, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)s2b, (int64_t)s2c, s2h,
-                       input2, gradoutput, gradinput1, tbox);
+    if (wq < w) launch_bwd_cn_zero_tail(k);
+    const auto flow = wq < w ? bl_bwd_flow_c4n<kCap, true> : bl_bwd_flow_c4n<kCap, false>;
+    hipLaunchKernelGGL(flow, dim3(ntiles), dim3(256), (tile_lds_bytes<16, kCap>() + 64), k.stream, w, h, wq, k.channel, ntx, nty,
+                       k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.in1, k.flow, k.gout, k.gin2, tbox);
+    launch_fi_bwd_image_owner<FpBilinear, 16, false>(k, Plane{0, 0, 0}, nullptr, tbox, nullptr);
+    if (wq < w)
+        hipLaunchKernelGGL(bl_bwd_tail_sites, dim3((unsigned)(((int64_t)k.batch * h * (w - wq) + 3) / 4)), dim3(256), 0, k.stream,
+                           w, h, wq, k.channel, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.in1, k.flow, k.gout,
+                           k.gin1, k.gin2);
+    hipLaunchKernelGGL(bl_bwd_far_sites, dim3(ntiles), dim3(256), 0, k.stream, w, h, wq, k.channel, ntx, nty, k.batch, k.s1.b,
+                       k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.flow, k.gout, k.gin1, tbox);
     return launch_status() == 0 ? 1 : -1;
 }
 

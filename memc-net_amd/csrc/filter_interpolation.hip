@@ -1164,10 +1164,7 @@ extern "C" int FilterInterpolationLayer_gpu_backward_kernel(
             return launch_status();
         }
         return taken > 0 ? 0 : -1;                         // RGB: fi_bwd_c3.hip
-    } else if (channel != 3 &&
-               (taken = fi_bwd_cn_launch(stream, w, h, channel, batch, s1b, s1c, s1h, s2b, s2c, s2h, s3b, s3c, s3h, input1,
-                                         input2, input3, gradoutput, gradinput1, gradinput2, gradinput3,
-                                         direct_only)) != 0) {
+    } else if (channel != 3 && (taken = fi_bwd_cn_launch(k, direct_only)) != 0) {
         MEMC_PATH("fi_bwd:owner");
         return taken > 0 ? 0 : -1;                         // many channels: fi_bwd_cn.hip
     } else if (channel == 3) {

@@ -1286,15 +1286,16 @@ __global__ void proj_stall(int us)
 // Owner kernel geometry of the product build (measured): tile height and stripe width of the walk.
 constexpr int kOwnerTH = 32, kOwnerSW = 4;
 
-struct ProjArgs {
-    hipStream_t stream;
-    int w, h, batch, fillhole;
-    int s1b, s1c, s1h, sdb, sdh, scb, sch;
-    const float *flow, *depth;
-    float *count, *out;
-    void *ws;                                    // caller's workspace (the _ws entry points) or nullptr: the library's own block
-    size_t ws_bytes;
-};
+// waves per SIMD the owner kernel's register allocator must leave room for = what the LDS admits: FlowProjection 4
+// workgroups per CU at TH = 32 (2 planes, 35 KiB), the depth operator 3 (53 KiB)
+// (the ragged-row instantiation needs a few registers more: two waves per SIMD fewer rather than a spill)
+template <bool DEPTH, int TH>
+constexpr int owner_min_waves(bool rag)
+{
+    constexpr int kWgCu = TH == 16 ? (DEPTH ? 4 : 6) : (TH == 32 ? (DEPTH ? 3 : 4) : 1);
+    constexpr int kMinW = (kWgCu * (16 * TH / 64) + 3) / 4 > 8 ? 8 : (kWgCu * (16 * TH / 64) + 3) / 4;
+    return rag && kMinW > 2 ? kMinW - 2 : kMinW;
+}
 
 // The call's scratch (library block or caller's workspace), in ints: [0, kHead) far flags (image b -> word b % 256, word
 // 256 = "any"), the tiles' far table (kFarWords ints per tile: proj_owner5.hpp), then -- with hole filling -- the three tables
@@ -1325,52 +1326,55 @@ static ProjWsLayout proj_ws_layout(int w, int h, int batch, bool fast, bool carr
 }
 
 // The far-source flags carry a per-call nonce instead of being cleared: ONE process-wide counter for every
-// instantiation of run_proj_fwd (a function-local static would give FlowProjection and DepthFlowProjection their own
-// counters, and two calls handed the same scratch block could carry the same nonce: a needless whole-image redo).
+// instantiation of proj_resolve (a function-local static would give each instantiation its own
+// counter, and two calls handed the same scratch block could carry the same nonce: a needless whole-image redo).
 static std::atomic<unsigned> g_proj_call_counter{0};
 
-// vectorised forward: owner-computes fast path (proj_owner5; images with a far source redone by proj_owner_far behind a
-// device flag), hole filling from masks (proj_fill.hpp), with the tile height TH of the owner kernel and the filler;
-// without scratch the general path (zero, scatter with atomics, average) and the literal hole walker.
-// variant: measurement build only (-1 otherwise).
-// RAG: a width that is not a multiple of four (the owner kernels' ragged-row instantiations; returns 1 -- not served, the
-// caller takes the scalar kernels -- where the fast path cannot run: no scratch block, a plane beyond 4 GiB).
-template <bool DEPTH, int TH, bool RAG = false>
-static int run_proj_fwd(const ProjArgs &a, int sw, int variant)
+// What a forward call resolved to before its first launch: the tile counts, the scratch block with the tables in it and the
+// nonce.  The product's sequence (run_proj_fwd) and the measurement arms (arms/proj_fwd_arms.hpp) both launch from it.
+struct ProjRun {
+    int ntx, nty, snty, sw;                  // owner tiles (64 x TH); the general path's 64 x 16 SOURCE tiles; the walk's stripe width
+    unsigned ntiles, sntiles;
+    ProjWsLayout lay;
+    CallScratch scratch;                     // the library's block: held until the call's last launch is queued
+    int *base;                               // the library's block or the caller's workspace (nullptr: none), then in it:
+    int *flag, *bounds, *stamps;             // far flags, the tiles' far table and stamps (nullptr: no fast path)
+    FillWs ws;                               // the hole filler's tables (ws.up == nullptr: the literal hole walker)
+    int nonce;                               // 0: the device counter (inside a stream capture)
+
+    // proj_fill_pending: workgroup i lists the flagged ones among the tiles i, i + grid, ... and its sixteen waves take
+    // one tile at a time; one workgroup per CU is what the chip holds at once (LDS, registers).  The grid is
+    // coprime to the tiles per row: the tiles of an image's left or right edge (a camera pan's uncovered band: the
+    // heavy ones) are tiles_x apart and would otherwise meet in a few workgroups.
+    unsigned fill_grid() const
+    {
+        constexpr unsigned kW = (unsigned)kFillWaves;
+        unsigned pg = (ntiles + kW - 1u) / kW < 256u ? (ntiles + kW - 1u) / kW : 256u;
+        auto coprime = [](unsigned x, unsigned y) {
+            while (y) {
+                const unsigned t = x % y;
+                x = y;
+                y = t;
+            }
+            return x == 1u;
+        };
+        while (pg > 1u && !coprime(pg, (unsigned)ntx)) pg--;
+        return pg;
+    }
+};
+
+// Layout, workspace or scratch block, nonce.  fast / carry / masks: what the call may use -- the measurement arms ask for
+// less (no owner path, the literal hole walker, round 3's summaries without masks).  0, or -1: a workspace that does not fit.
+template <int TH>
+static int proj_resolve(const ProjFwdCall &a, int sw, ProjRun &r, bool fast = true, bool carry = true, bool masks = true)
 {
-    using A = AccGeom<16>;
-    const hipStream_t stream = a.stream;
-    const int w = a.w, h = a.h, batch = a.batch;
-    const int ntx = (w + 63) / 64, nty = (h + TH - 1) / TH;
-    const unsigned ntiles = (unsigned)ntx * nty * batch;
-    const int snty = (h + 15) / 16;                          // the general path scatters from 64x16 SOURCE tiles
-    const unsigned sntiles = (unsigned)ntx * snty * batch;
-    const unsigned gs = 256 * 8;                             // grid-stride: 8 workgroups per CU
-    const int64_t s1b = a.s1b, s1c = a.s1c, sdb = a.sdb, scb = a.scb;
-    const int s1h = a.s1h, sdh = a.sdh, sch = a.sch;
-
-    // which set of kernels (measurement build: the rounds 1-3 arms keep their own summaries and filler)
-    bool r3_set = false;                                     // proj_owner4 / proj_owner_far_r3 / proj_fillhole_carry
-    bool legacy_owner = false;                               // proj_owner, proj_owner2, proj_owner3 (+ general path behind the flag)
-#ifdef MEMC_MEASURE
-    r3_set = variant == -40 || variant == -20;
-    legacy_owner = variant == -10 || variant == -7 || variant == -6 || variant == -30 || variant == -31 ||
-                   (variant <= -21 && variant >= -29);
-#endif
-    constexpr bool kNewOk = TH <= 32;                        // a column mask of proj_fill.hpp is one 32-bit word
-    if (!kNewOk && !legacy_owner) return -1;
-    const bool old_fill = r3_set || legacy_owner;
-
+    r.ntx = (a.w + 63) / 64;  r.nty = (a.h + TH - 1) / TH;  r.snty = (a.h + 15) / 16;  r.sw = sw;
+    r.ntiles = (unsigned)r.ntx * r.nty * a.batch;
+    r.sntiles = (unsigned)r.ntx * r.snty * a.batch;
     // (the owner kernel addresses the flow / depth planes with 32-bit offsets)
-    const bool want_fast = variant != 1 && variant < 2 && plane_fits_u32(w, h, {s1h, sdh}) && ntiles <= (unsigned)far_max_tiles<TH>();
-    const bool want_carry = a.fillhole && variant != -8 && variant != -9;
-    // scratch layout: ProjWsLayout above
-    constexpr size_t kHead = kProjWsHead;
-    const ProjWsLayout lay = proj_ws_layout<TH>(w, h, batch, want_fast, want_carry, !old_fill);
-    const size_t n_bnd = lay.n_bnd, n_up = lay.n_up, n_row = lay.n_row, ints = lay.ints;
-    CallScratch scratch;
-    int *flag = nullptr, *bounds = nullptr, *stamps = nullptr;
-    FillWs ws = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const bool want_fast = fast && plane_fits_u32(a.w, a.h, {a.s1.h, a.sd.h}) && r.ntiles <= (unsigned)far_max_tiles<TH>();
+    const bool want_carry = a.fillhole && carry;
+    r.lay = proj_ws_layout<TH>(a.w, a.h, a.batch, want_fast, want_carry, masks);
     // The production pair (proj_owner5 / proj_owner_far) needs no cleared flag words: a flag is "raised" when it holds
     // this call's nonce -- a process-wide counter, never 0, so consecutive calls (which the pool hands the same block)
     // never see each other's flags; a stale or uninitialised word equal to the nonce would only cause a needless redo (and
@@ -1380,374 +1384,220 @@ static int run_proj_fwd(const ProjArgs &a, int sw, int variant)
     if (nonce_u == 0) nonce_u = g_proj_call_counter.fetch_add(1, std::memory_order_relaxed) + 1u;
     // (sign bit set: the block is reused across calls of different shapes and holds row / column indices, hole flags, -1 --
     // a small sequential tag could meet one of those in a stale word and cause a needless recomputation)
-    int nonce = (int)((nonce_u & 0x7fffffffu) | 0x80000000u);
-    if (nonce == -1) nonce = (int)0x80000000u;
+    r.nonce = (int)((nonce_u & 0x7fffffffu) | 0x80000000u);
+    if (r.nonce == -1) r.nonce = (int)0x80000000u;
     if (a.ws) {                                              // (only a caller's workspace can be inside a capture at all)
         hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &capture) != hipSuccess) (void)hipGetLastError();
-        if (capture != hipStreamCaptureStatusNone) nonce = 0;            // the device counter: proj_bump_nonce
+        if (hipStreamIsCapturing(a.stream, &capture) != hipSuccess) (void)hipGetLastError();
+        if (capture != hipStreamCaptureStatusNone) r.nonce = 0;          // the device counter: proj_bump_nonce
     }
     // A caller's workspace (the _ws entry points: memc_flow_projection_workspace_bytes says how much) replaces the library's
     // block -- nothing is allocated, nothing is kept, a stream capture takes the same kernels as an eager call.
-    if (a.ws && (a.ws_bytes < lay.bytes() || (reinterpret_cast<uintptr_t>(a.ws) & 15u) != 0)) return -1;
+    if (a.ws && (a.ws_bytes < r.lay.bytes() || (reinterpret_cast<uintptr_t>(a.ws) & 15u) != 0)) return -1;
     void *block = nullptr;
     if (want_fast || want_carry) {
         if (a.ws) block = a.ws;
-        else if (scratch.alloc(lay.bytes(), stream, g_proj_scratch_blocks)) block = scratch.p;
+        else if (r.scratch.alloc(r.lay.bytes(), a.stream, g_proj_scratch_blocks)) block = r.scratch.p;
     }
-    if (block) {
-        int *base = static_cast<int *>(block);
-        if (legacy_owner && hipMemsetAsync(base, 0, kHead * sizeof(int), stream) != hipSuccess) return -1;
-        if (want_fast) {
-            flag = base;
-            bounds = base + kHead;
-            stamps = bounds + kFarWords * (size_t)ntiles;
-        }
-        if (want_carry) {
-            ws.up = base + kHead + n_bnd;
-            ws.left = ws.up + n_up;
-            ws.right = ws.left + n_row;
-            ws.hole = ws.right + n_row;
-            ws.masks = reinterpret_cast<unsigned long long *>(base + ints);
-        }
+    r.base = static_cast<int *>(block);
+    r.flag = r.bounds = r.stamps = nullptr;
+    r.ws = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (block && want_fast) {
+        r.flag = r.base;
+        r.bounds = r.base + kProjWsHead;
+        r.stamps = r.bounds + kFarWords * (size_t)r.ntiles;
     }
+    if (block && want_carry) {
+        r.ws.up = r.base + kProjWsHead + r.lay.n_bnd;
+        r.ws.left = r.ws.up + r.lay.n_up;
+        r.ws.right = r.ws.left + r.lay.n_row;
+        r.ws.hole = r.ws.right + r.lay.n_row;
+        r.ws.masks = reinterpret_cast<unsigned long long *>(r.base + r.lay.ints);
+    }
+    return 0;
+}
+
+// ---- launch functions of the forward's kernel families: grid, workgroup size and argument list, spelled once ----
+template <bool DEPTH, int TH, int MINW, bool TRACE = false, bool FIX64 = false, bool RAG = false, int MOT = 0, int PENDT = -1>
+static void launch_proj_owner5(const ProjFwdCall &a, const ProjRun &r, const WalkPlan &plan)
+{
+    hipLaunchKernelGGL((proj_owner5<DEPTH, TH, 24, MINW, TRACE, FIX64, RAG, MOT, PENDT>), dim3(plan.nwg), dim3(16 * TH), 0, a.stream,
+                       a.w, a.h, r.ntx, r.nty, a.s1.b, a.s1.c, a.s1.h, a.sd.b, a.sd.h, a.sc.b, a.sc.h, a.flow, a.depth, a.count,
+                       a.out, r.flag, r.bounds, r.stamps, r.ws, plan, r.nonce);
+}
+
+template <bool DEPTH, int TH, bool RAG>
+static void launch_proj_owner_far(const ProjFwdCall &a, const ProjRun &r)
+{
+    // (53 KiB of LDS, 114 VGPRs: two per CU; a lane of the grid per stamped tile at most: proj_owner_far's work list)
+    const unsigned pg = persistent_grid(2), need = (r.ntiles + 16u * TH - 1u) / (16u * TH), fg0 = r.ntiles < pg ? r.ntiles : pg;
+    hipLaunchKernelGGL((proj_owner_far<DEPTH, TH, 24, 4, 16 * TH, RAG>), dim3(fg0 > need ? fg0 : need), dim3(16 * TH), 0, a.stream,
+                       a.w, a.h, r.ntx, r.nty, a.batch, a.s1.b, a.s1.c, a.s1.h, a.sd.b, a.sd.h, a.sc.b, a.sc.h, a.flow, a.depth,
+                       a.count, a.out, r.flag, r.bounds, r.stamps, r.ws, r.nonce);
+}
+
+// the general path's three passes; flag: only the images whose far flag is raised (the measurement build's older owners)
+template <class K>                              // proj_redo_zero before the scatter, proj_average_v4 behind it: the same arguments
+static void launch_proj_plane_pass(K kernel, const ProjFwdCall &a, unsigned grid, const int *flag)
+{
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, a.stream, a.w, a.h, a.s1.b, a.s1.c, a.s1.h, a.sc.b, a.sc.h, a.batch,
+                       a.count, a.out, flag);
+}
+
+template <bool DEPTH, int ABL>
+static void launch_proj_scatter_tiled(const ProjFwdCall &a, const ProjRun &r, const int *flag, unsigned grid)
+{
+    hipLaunchKernelGGL((proj_scatter_tiled<DEPTH, ABL>), dim3(grid), dim3(256), 4 * AccGeom<16>::kPlane * 4 + 64, a.stream, a.w,
+                       a.h, r.ntx, r.snty, r.sntiles, a.s1.b, a.s1.c, a.s1.h, a.sd.b, a.sd.h, a.sc.b, a.sc.h, a.flow, a.depth,
+                       a.count, a.out, flag);
+}
+
+template <int TH>
+static void launch_proj_fill_masks(const ProjFwdCall &a, const ProjRun &r, unsigned max_grid)
+{
+    hipLaunchKernelGGL(proj_fill_masks<TH>, dim3(r.ntiles < max_grid ? r.ntiles : max_grid), dim3(16 * TH), 0, a.stream, a.w,
+                       a.h, r.ntx, r.nty, a.batch, a.sc.b, a.sc.h, a.count, r.ws);
+}
+
+template <int TH>
+static void launch_proj_fill_pending(const ProjFwdCall &a, const ProjRun &r)
+{
+    hipLaunchKernelGGL(proj_fill_pending<TH>, dim3(r.fill_grid()), dim3(kFillWaves * kWave), 0, a.stream, a.w, a.h, r.ntx, r.nty,
+                       a.batch, a.s1.b, a.s1.c, a.s1.h, a.sc.b, a.sc.h, a.count, a.out, r.ws);
+}
+
+static void launch_proj_fillhole_v4(const ProjFwdCall &a, const ProjRun &r, int literal)
+{
+    hipLaunchKernelGGL(proj_fillhole_v4, dim3(r.sntiles), dim3(256), 0, a.stream, a.w, a.h, r.ntx, r.snty, a.s1.b, a.s1.c,
+                       a.s1.h, a.sc.b, a.sc.h, a.count, a.out, literal);
+}
+
+// vectorised forward: owner-computes fast path (proj_owner5; images with a far source redone by proj_owner_far behind a
+// device flag), hole filling from masks (proj_fill.hpp), with the tile height TH of the owner kernel and the filler;
+// without scratch the general path (zero, scatter with atomics, average) and the literal hole walker.
+// RAG: a width that is not a multiple of four (the owner kernels' ragged-row instantiations; returns 1 -- not served, the
+// caller takes the scalar kernels -- where the fast path cannot run: no scratch block, a plane beyond 4 GiB).
+template <bool DEPTH, int TH, bool RAG = false>
+static int run_proj_fwd(const ProjFwdCall &a, int sw)
+{
+    static_assert(TH <= 32, "a column mask of proj_fill.hpp is one 32-bit word");
+    ProjRun r;
+    if (proj_resolve<TH>(a, sw, r) != 0) return -1;
     // Without scratch (inside a stream capture, or the allocation failed): the general path on its own and the
     // literal hole walker -- slower, same results.
-    if (RAG && !(flag && (ws.up || !a.fillhole))) return 1;  // (the general path's kernels want whole quads: scalar kernels instead)
-
-#define MEMC_PROJ_SCATTER(ABL, FLAG)                                                                        \
-    hipLaunchKernelGGL((proj_scatter_tiled<DEPTH, ABL>), dim3((FLAG) != nullptr && sntiles > gq ? gq : sntiles), \
-                       dim3(256), 4 * A::kPlane * 4 + 64, stream, w, h, ntx, snty, sntiles, s1b, s1c, s1h, sdb, sdh,  \
-                       scb, sch, a.flow, a.depth, a.count, a.out, FLAG)
-    bool only_part = false, skip_pending = false;            // measurement arms that time one piece
-    MEMC_PATH(flag ? (DEPTH ? "dproj_fwd:owner" : "proj_fwd:owner") : (DEPTH ? "dproj_fwd:general" : "proj_fwd:general"));
-    // waves per SIMD the register allocator must leave room for = what the LDS admits: FlowProjection 4 workgroups per
-    // CU at TH = 32 (2 planes, 35 KiB), the depth operator 3 (53 KiB)
-    constexpr int kWgCu = TH == 16 ? (DEPTH ? 4 : 6) : (TH == 32 ? (DEPTH ? 3 : 4) : 1);
-    constexpr int kMinW = (kWgCu * (16 * TH / 64) + 3) / 4 > 8 ? 8 : (kWgCu * (16 * TH / 64) + 3) / 4;
-    // (the ragged-row instantiation needs a few registers more: two waves per SIMD fewer rather than a spill)
-    [[maybe_unused]] constexpr int kMinWR = RAG && kMinW > 2 ? kMinW - 2 : kMinW;
-    if (flag && !legacy_owner) {
-        if constexpr (kNewOk) {
-            if (nonce == 0) hipLaunchKernelGGL(proj_bump_nonce, dim3(1), dim3(1), 0, stream, flag);
-            WalkPlan plan = make_walk_plan(ntx, nty, batch, sw);
-#ifdef MEMC_MEASURE
-            if (variant == -43) plan.fast = 0;      // test arm: the kernel's own tile_walk (what grids beyond n * d < 2^32 take)
-#endif
-#ifdef MEMC_MEASURE
-            only_part = variant == -5 || variant == -20 || variant == -41;
-            skip_pending = variant == -42;          // timing arm: everything but proj_fill_pending (pending holes stay unfilled)
-            if (r3_set) {
-                hipLaunchKernelGGL((proj_owner4<DEPTH, TH, 24, kMinW>), dim3(walk_grid(ntx, nty, batch, sw)), dim3(16 * TH),
-                                   0, stream, w, h, ntx, nty, s1b, s1c, s1h, sdb, sdh, scb, sch, a.flow, a.depth, a.count,
-                                   a.out, flag, bounds, ws, sw, nonce);
-            } else if (variant == -46 && DEPTH) {   // timing arm: 64-bit fixed-point planes on ds_add_u64 (proj_owner5.hpp, FIX64)
-                hipLaunchKernelGGL((proj_owner5<DEPTH, TH, 24, kMinW, false, true>), dim3(plan.nwg), dim3(16 * TH), 0, stream, w, h,
-                                   ntx, nty, s1b, s1c, s1h, sdb, sdh, scb, sch, a.flow, a.depth, a.count, a.out, flag,
-                                   bounds, stamps, ws, plan, nonce);
-            } else if ((variant <= -47 && variant >= -50) || variant == -54) {   // how the motion estimate reaches the scan (proj_owner5.hpp, MOT):
-#define MEMC_PROJ_MOT(M)                                                                                              \
-                hipLaunchKernelGGL((proj_owner5<DEPTH, TH, 24, kMinWR, false, false, RAG, M>), dim3(plan.nwg), dim3(16 * TH), 0, stream, \
-                                   w, h, ntx, nty, s1b, s1c, s1h, sdb, sdh, scb, sch, a.flow, a.depth, a.count, a.out, flag,  \
-                                   bounds, stamps, ws, plan, nonce)
-                if (variant == -47) MEMC_PROJ_MOT(1);         // -47: speculative m = 0 pass, samples by LDS DMA (round 6, lost)
-                else if (variant == -48) MEMC_PROJ_MOT(2);    // -48: no estimate (timing arm)
-                else if (variant == -49) MEMC_PROJ_MOT(3);    // -49: 16 samples, one lane each (timing arm)
-                else if (variant == -50) MEMC_PROJ_MOT(4);    // -50: 16 samples through the scalar unit (timing arm)
-                else MEMC_PROJ_MOT(5);                        // -54: the estimate cached per image in the call's scratch
-#undef MEMC_PROJ_MOT
-            } else if (variant <= -51 && variant >= -53) {   // tiles with many holes leave ALL of them pending (proj_fill.hpp, PENDT)
-#define MEMC_PROJ_PENDT(T)                                                                                            \
-                hipLaunchKernelGGL((proj_owner5<DEPTH, TH, 24, kMinWR, false, false, RAG, 0, T>), dim3(plan.nwg), dim3(16 * TH), 0, stream, \
-                                   w, h, ntx, nty, s1b, s1c, s1h, sdb, sdh, scb, sch, a.flow, a.depth, a.count, a.out, flag,  \
-                                   bounds, stamps, ws, plan, nonce)
-                if (variant == -51) MEMC_PROJ_PENDT(0);       // -51: every tile with a hole
-                else if (variant == -52) MEMC_PROJ_PENDT(8);  // -52: more than 8 lanes with a hole
-                else MEMC_PROJ_PENDT(32);                     // -53: more than 32
-#undef MEMC_PROJ_PENDT
-            } else if (variant == -41) {       // timestamps (tools/trace_kernel.py proj5)
-                hipLaunchKernelGGL((proj_owner5<DEPTH, TH, 24, kMinW, true>), dim3(plan.nwg), dim3(16 * TH), 0, stream, w, h,
-                                   ntx, nty, s1b, s1c, s1h, sdb, sdh, scb, sch, a.flow, a.depth, a.count, a.out, flag,
-                                   bounds, stamps, ws, plan, nonce);
-            } else
-#endif
-            hipLaunchKernelGGL((proj_owner5<DEPTH, TH, 24, kMinWR, false, false, RAG>), dim3(plan.nwg), dim3(16 * TH), 0, stream, w,
-                               h, ntx, nty, s1b, s1c, s1h, sdb, sdh, scb, sch, a.flow, a.depth, a.count, a.out, flag, bounds, stamps, ws,
-                               plan, nonce);
-            if (launch_status() != 0) return -1;
-#ifdef MEMC_MEASURE
-            if (g_proj_stall_us > 0) hipLaunchKernelGGL(proj_stall, dim3(1), dim3(64), 0, stream, g_proj_stall_us);
-#endif
-            if (!only_part) {
-                const unsigned pg = r3_set ? persistent_grid(1) : persistent_grid(2);   // (53 KiB of LDS, 114 VGPRs: two per CU)
-#ifdef MEMC_MEASURE
-                if (r3_set)
-                    hipLaunchKernelGGL((proj_owner_far_r3<DEPTH, TH, 24>), dim3(ntiles < pg ? ntiles : pg), dim3(16 * TH), 0,
-                                       stream, w, h, ntx, nty, batch, s1b, s1c, s1h, sdb, sdh, scb, sch, a.flow, a.depth,
-                                       a.count, a.out, flag, bounds, ws, nonce);
-                else
-#endif
-                {   // (a lane of the grid per stamped tile at most: proj_owner_far's work list)
-                    const unsigned need = (ntiles + 16u * TH - 1u) / (16u * TH), fg0 = ntiles < pg ? ntiles : pg;
-                    hipLaunchKernelGGL((proj_owner_far<DEPTH, TH, 24, 4, 16 * TH, RAG>), dim3(fg0 > need ? fg0 : need), dim3(16 * TH), 0, stream,
-                                       w, h, ntx, nty, batch, s1b, s1c, s1h, sdb, sdh, scb, sch, a.flow, a.depth, a.count,
-                                       a.out, flag, bounds, stamps, ws, nonce);
-                }
-                if (launch_status() != 0) return -1;
-            }
-        }
-    }
-#ifdef MEMC_MEASURE
-    else if (flag) {
-        // rounds 1-2 owner kernels: 0 / 1 flags, flagged images redone by the general path queued behind the flag
-        const unsigned gq = 256 * 2;
-        bool launched = false;
-        if (variant == -10 || variant == -7 || variant == -6) {       // round-1 owner kernel (64x16, strips)
-            const unsigned nwg = ntiles;
-#define MEMC_PROJ_OWNER(REACH, TRACE)                                                                              \
-            hipLaunchKernelGGL((proj_owner<DEPTH, REACH, TRACE>), dim3(nwg), dim3(256), 0, stream, w, h, ntx, nty, s1b, \
-                               s1c, s1h, sdb, sdh, scb, sch, a.flow, a.depth, a.count, a.out, flag, ws)
-            if (TH == 16) {
-                if (variant == -7) MEMC_PROJ_OWNER(24, true);
-                else if (variant == -6) MEMC_PROJ_OWNER(16, false);
-                else MEMC_PROJ_OWNER(24, false);
-                launched = true;
-            }
-#undef MEMC_PROJ_OWNER
-        }
-        only_part = variant == -7;
-#define MEMC_PROJ_OWNER2(ABL, TRACE)                                                                              \
-            hipLaunchKernelGGL((proj_owner2<DEPTH, TH, 24, ABL, TRACE>), dim3(walk_grid(ntx, nty, batch, sw)),          \
-                               dim3(16 * TH), 0, stream, w, h, ntx, nty, s1b, s1c, s1h, sdb, sdh, scb, sch, a.flow,       \
-                               a.depth, a.count, a.out, flag, ws, sw)
-        if (!launched && variant <= -21 && variant > -30) {   // -21 .. -26: timing arms of proj_owner2 (wrong results); -29: timestamps
-            only_part = true;
-            launched = true;
-            if (variant == -21) MEMC_PROJ_OWNER2(1, false);
-            else if (variant == -22) MEMC_PROJ_OWNER2(2, false);
-            else if (variant == -23) MEMC_PROJ_OWNER2(3, false);
-            else if (variant == -24) MEMC_PROJ_OWNER2(4, false);
-            else if (variant == -25) MEMC_PROJ_OWNER2(5, false);
-            else if (variant == -26) MEMC_PROJ_OWNER2(6, false);
-            else if (variant == -29) MEMC_PROJ_OWNER2(0, true);
-            else launched = false;
-        }
-        if (!launched && variant == -30) {     // proj_owner2: LDS rings, three planes
-            MEMC_PROJ_OWNER2(0, false);
-            launched = true;
-        }
-        if (!launched && variant == -31) {     // proj_owner3: persistent, next tile's fy prefetched
-            if constexpr (TH == 32) {
-                const unsigned npos = walk_grid(ntx, nty, batch, sw), pg = persistent_grid(2);
-                hipLaunchKernelGGL((proj_owner3<DEPTH, 32, 24, 2>), dim3(npos < pg ? (npos + 7) / 8 * 8 : pg), dim3(512), 0,
-                                   stream, w, h, ntx, nty, npos, s1b, s1c, s1h, sdb, sdh, scb, sch, a.flow, a.depth,
-                                   a.count, a.out, flag, ws, sw);
-                launched = true;
-            }
-        }
-#undef MEMC_PROJ_OWNER2
-        if (!launched) return -1;
+    if (RAG && !(r.flag && (r.ws.up || !a.fillhole))) return 1;  // (the general path's kernels want whole quads: scalar kernels instead)
+    MEMC_PATH(r.flag ? (DEPTH ? "dproj_fwd:owner" : "proj_fwd:owner") : (DEPTH ? "dproj_fwd:general" : "proj_fwd:general"));
+    if (r.flag) {
+        if (r.nonce == 0) hipLaunchKernelGGL(proj_bump_nonce, dim3(1), dim3(1), 0, a.stream, r.flag);
+        launch_proj_owner5<DEPTH, TH, owner_min_waves<DEPTH, TH>(RAG), false, false, RAG>(a, r, make_walk_plan(r.ntx, r.nty, a.batch, sw));
         if (launch_status() != 0) return -1;
-        if (!only_part) {
-            hipLaunchKernelGGL(proj_redo_zero, dim3(gq), dim3(256), 0, stream, w, h, s1b, s1c, s1h, scb, sch, batch,
-                               a.count, a.out, flag);
-            MEMC_PROJ_SCATTER(0, flag);
-            hipLaunchKernelGGL(proj_average_v4, dim3(gq), dim3(256), 0, stream, w, h, s1b, s1c, s1h, scb, sch, batch,
-                               a.count, a.out, flag);
-            if (ws.up)                          // summaries of the images the general path redid
-                hipLaunchKernelGGL(proj_fill_summary<TH>, dim3(gq), dim3(256), 0, stream, w, h, ntx, nty, batch, scb,
-                                   sch, a.count, ws, flag);
-            if (launch_status() != 0) return -1;
-        }
-    }
+#ifdef MEMC_MEASURE
+        if (g_proj_stall_us > 0) hipLaunchKernelGGL(proj_stall, dim3(1), dim3(64), 0, a.stream, g_proj_stall_us);
 #endif
-    else {
+        launch_proj_owner_far<DEPTH, TH, RAG>(a, r);
+    } else {
         // the general path on its own: it DEFINES count and output (zero, scatter, average), it does not rely on
         // the caller's zero fill
-        const unsigned gq = 0;                 // (unused: no flag)
-        (void)gq;
-#ifdef MEMC_MEASURE
-        only_part = variant >= 2;               // (the ablation arms 2 / 3 time the scatter pass alone)
-        if (variant == 2) MEMC_PROJ_SCATTER(2, (const int *)nullptr);
-        else if (variant == 3) MEMC_PROJ_SCATTER(3, (const int *)nullptr);
-#endif
-        if (!only_part) {
-            hipLaunchKernelGGL(proj_redo_zero, dim3(gs), dim3(256), 0, stream, w, h, s1b, s1c, s1h, scb, sch, batch,
-                               a.count, a.out, (const int *)nullptr);
-            MEMC_PROJ_SCATTER(0, (const int *)nullptr);
-            hipLaunchKernelGGL(proj_average_v4, dim3(gs), dim3(256), 0, stream, w, h, s1b, s1c, s1h, scb, sch, batch,
-                               a.count, a.out, (const int *)nullptr);
-            if (ws.up) {
-#ifdef MEMC_MEASURE
-                if (old_fill)
-                    hipLaunchKernelGGL(proj_fill_summary<TH>, dim3(gs), dim3(256), 0, stream, w, h, ntx, nty, batch, scb,
-                                       sch, a.count, ws, (const int *)nullptr);
-                else
-#endif
-                if constexpr (kNewOk)
-                    hipLaunchKernelGGL(proj_fill_masks<TH>, dim3(ntiles < gs ? ntiles : gs), dim3(16 * TH), 0, stream, w, h,
-                                       ntx, nty, batch, scb, sch, a.count, ws);
-            }
-        }
-        if (launch_status() != 0) return -1;
+        const unsigned gs = 256 * 8;                         // grid-stride: 8 workgroups per CU
+        launch_proj_plane_pass(proj_redo_zero, a, gs, nullptr);
+        launch_proj_scatter_tiled<DEPTH, 0>(a, r, nullptr, r.sntiles);
+        launch_proj_plane_pass(proj_average_v4, a, gs, nullptr);
+        if (r.ws.up) launch_proj_fill_masks<TH>(a, r, gs);
     }
-#undef MEMC_PROJ_SCATTER
-    if (a.fillhole && !only_part && !skip_pending) {
-        if (ws.up) {
-            // round 3's filler: workgroup i looks after the tiles i, i + grid, ... (one flag per lane of a wave)
-            [[maybe_unused]] const unsigned fg = ntiles < 4096u ? ntiles : (ntiles + 63u) / 64u > 4096u ? (ntiles + 63u) / 64u : 4096u;
-            // proj_fill_pending: workgroup i lists the flagged ones among the tiles i, i + grid, ... and its sixteen waves take
-            // one tile at a time; one workgroup per CU is what the chip holds at once (LDS, registers).  The grid is
-            // coprime to the tiles per row: the tiles of an image's left or right edge (a camera pan's uncovered band: the
-            // heavy ones) are tiles_x apart and would otherwise meet in a few workgroups.
-            constexpr unsigned kW = (unsigned)kFillWaves;
-            unsigned pg = (ntiles + kW - 1u) / kW < 256u ? (ntiles + kW - 1u) / kW : 256u;
-            auto coprime = [](unsigned x, unsigned y) {
-                while (y) {
-                    const unsigned t = x % y;
-                    x = y;
-                    y = t;
-                }
-                return x == 1u;
-            };
-            while (pg > 1u && !coprime(pg, (unsigned)ntx)) pg--;
-#ifdef MEMC_MEASURE
-            if (old_fill)
-                hipLaunchKernelGGL(proj_fillhole_carry<TH>, dim3(fg), dim3(256), 0, stream, w, h, ntx, nty, batch, s1b, s1c,
-                                   s1h, scb, sch, a.count, a.out, ws);
-            else
-#endif
-            if constexpr (kNewOk)
-                hipLaunchKernelGGL(proj_fill_pending<TH>, dim3(pg), dim3(kFillWaves * kWave), 0, stream, w, h, ntx, nty, batch, s1b, s1c, s1h,
-                                   scb, sch, a.count, a.out, ws);
-        } else {
-            hipLaunchKernelGGL(proj_fillhole_v4, dim3(sntiles), dim3(256), 0, stream, w, h, ntx, snty, s1b, s1c, s1h,
-                               scb, sch, a.count, a.out, variant == -8 ? 1 : 0);
-        }
+    if (launch_status() != 0) return -1;
+    if (a.fillhole) {
+        if (r.ws.up) launch_proj_fill_pending<TH>(a, r);
+        else launch_proj_fillhole_v4(a, r, 0);
         if (launch_status() != 0) return -1;
     }
     return 0;
 }
 
+#ifdef MEMC_MEASURE
+#include "arms/proj_fwd_arms.hpp"        // the arms' launch functions and proj_fwd_arm_launch: measurement build only
+#endif
+
 template <bool DEPTH>
-static int launch_proj_fwd(hipStream_t stream, int w, int h, int batch, int fillhole,
-                           int s1b, int s1c, int s1h, int sdb, int sdh, int scb, int sch,
-                           const float *flow, const float *depth, float *count, float *out,
-                           void *ws = nullptr, size_t ws_bytes = 0)
+static int launch_proj_fwd(const ProjFwdCall &a)
 {
-    if (w <= 0 || h <= 0 || batch <= 0) return 0;
-    const bool vec = vec4_ok(w, {s1b, s1c, s1h, sdb, sdh, scb, sch}, {flow, depth, count, out});
+    const int w = a.w, h = a.h;
+    if (w <= 0 || h <= 0 || a.batch <= 0) return 0;
+    const bool vec = vec4_ok(w, {a.s1.b, a.s1.c, a.s1.h, a.sd.b, a.sd.h, a.sc.b, a.sc.h}, {a.flow, a.depth, a.count, a.out});
     if (!vec && w >= 8 && g_proj_variant < 0) {            // a ragged width: the owner kernels' RAG instantiations (round 5)
-        const ProjArgs a = {stream, w, h, batch, fillhole, s1b, s1c, s1h, sdb, sdh, scb, sch, flow, depth, count, out,
-                            ws, ws_bytes};
-        const int r = run_proj_fwd<DEPTH, kOwnerTH, true>(a, kOwnerSW, -1);
+        const int r = run_proj_fwd<DEPTH, kOwnerTH, true>(a, kOwnerSW);
         if (r <= 0) return r;                                // served (0) or failed (-1); 1: the scalar kernels below
     }
     if (vec && g_proj_variant != 0) {
-        const ProjArgs a = {stream, w, h, batch, fillhole, s1b, s1c, s1h, sdb, sdh, scb, sch, flow, depth, count, out,
-                            ws, ws_bytes};
 #ifdef MEMC_MEASURE
-        // 100 + 10 * log2(TH / 16) + stripe width: owner geometry under test; -10 / -7 / -6: the round-1 owner
-        int v = g_proj_variant, th = kOwnerTH, sw = kOwnerSW;
-        if (v >= 100 && v < 120) {             // the production kernel (proj_owner5) in another geometry (TH 16 / 32)
-            th = 16 << ((v - 100) / 10);
-            sw = (v - 100) % 10;
-            v = -1;
-        } else if (v >= 400 && v < 420) {      // round 3's production set (proj_owner4 + carry filler), same geometry code + 300
-            th = 16 << ((v - 400) / 10);
-            sw = (v - 400) % 10;
-            v = -40;
-        } else if (v >= 130 && v < 160) {      // proj_owner2 (LDS rings, three planes), same geometry code + 30
-            th = 16 << ((v - 130) / 10);
-            sw = (v - 130) % 10;
-            v = -30;
-        } else if (v >= 160 && v < 170) {      // proj_owner3 (persistent, TH = 32), stripe width v - 160
-            th = 32;
-            sw = v - 160;
-            v = -31;
-        } else if (v == -10 || v == -7 || v == -6) {
-            th = 16;
-            sw = 0;
-        } else if (v >= 200 && v < 300) {      // 200 + 10 * arm + log2(TH / 16): timing arms / timestamps of proj_owner2
-            th = 16 << (v % 10);
-            sw = 0;
-            v = -(20 + (v - 200) / 10);
-        }
-        if (th == 16) return run_proj_fwd<DEPTH, 16>(a, sw, v);
-        if (th == 64) return run_proj_fwd<DEPTH, 64>(a, sw, v);
-        return run_proj_fwd<DEPTH, 32>(a, sw, v);
-#else
-        return run_proj_fwd<DEPTH, kOwnerTH>(a, kOwnerSW, -1);
+        if (const int arm = proj_fwd_arm_launch<DEPTH>(g_proj_variant, a)) return arm > 0 ? 0 : -1;
 #endif
+        return run_proj_fwd<DEPTH, kOwnerTH>(a, kOwnerSW);
     }
     const int tiles_x = (w + kWave - 1) / kWave, tiles_y = (h + 3) / 4;
-    const unsigned nwg = (unsigned)tiles_x * tiles_y * batch;
+    const unsigned nwg = (unsigned)tiles_x * tiles_y * a.batch;
     MEMC_PATH(DEPTH ? "dproj_fwd:scalar" : "proj_fwd:scalar");
-    hipLaunchKernelGGL(proj_zero_scalar, dim3(256 * 8), dim3(256), 0, stream, w, h, batch, (int64_t)s1b, (int64_t)s1c, s1h,
-                       (int64_t)scb, sch, count, out);
-    hipLaunchKernelGGL(proj_scatter<DEPTH>, dim3(nwg), dim3(256), 0, stream, w, h, tiles_x, tiles_y,
-                       (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)sdb, sdh, (int64_t)scb, sch, flow, depth, count, out);
+    hipLaunchKernelGGL(proj_zero_scalar, dim3(256 * 8), dim3(256), 0, a.stream, w, h, a.batch, a.s1.b, a.s1.c, a.s1.h, a.sc.b,
+                       a.sc.h, a.count, a.out);
+    hipLaunchKernelGGL(proj_scatter<DEPTH>, dim3(nwg), dim3(256), 0, a.stream, w, h, tiles_x, tiles_y, a.s1.b, a.s1.c, a.s1.h,
+                       a.sd.b, a.sd.h, a.sc.b, a.sc.h, a.flow, a.depth, a.count, a.out);
     if (launch_status() != 0) return -1;
-    hipLaunchKernelGGL(proj_average, dim3(nwg), dim3(256), 0, stream, w, h, tiles_x, tiles_y,
-                       (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)scb, sch, count, out);
+    hipLaunchKernelGGL(proj_average, dim3(nwg), dim3(256), 0, a.stream, w, h, tiles_x, tiles_y, a.s1.b, a.s1.c, a.s1.h, a.sc.b,
+                       a.sc.h, a.count, a.out);
     if (launch_status() != 0) return -1;
-    if (fillhole) {
-        hipLaunchKernelGGL(proj_fillhole, dim3(nwg), dim3(256), 0, stream, w, h, tiles_x, tiles_y,
-                           (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)scb, sch, count, out);
+    if (a.fillhole) {
+        hipLaunchKernelGGL(proj_fillhole, dim3(nwg), dim3(256), 0, a.stream, w, h, tiles_x, tiles_y, a.s1.b, a.s1.c, a.s1.h,
+                           a.sc.b, a.sc.h, a.count, a.out);
         if (launch_status() != 0) return -1;
     }
     return 0;
 }
 
-template <bool DEPTH>
-static int launch_proj_bwd(hipStream_t stream, int w, int h, int batch,
-                           int s1b, int s1c, int s1h, int sdb, int sdh, int scb, int sch,
-                           const float *flow, const float *depth, const float *count, const float *fwd_out,
-                           const float *gout, float *gin1, float *gin2)
+// the tiled backward over the whole quads of a row (sites x < w & ~3)
+template <bool DEPTH, int CAP>
+static void launch_proj_bwd_tiled(const ProjBwdCall &k)
 {
-    if (w <= 0 || h <= 0 || batch <= 0) return 0;
-    const bool vec = vec4_ok(w, {s1b, s1c, s1h, sdb, sdh, scb, sch}, {flow, depth, count, fwd_out, gout, gin1, gin2});
+    using G = TileGeom<16>;
+    const int ws = k.w & ~3, sw = g_tile_walk_sw >= 0 ? g_tile_walk_sw : kDefaultStripe;
+    const int ntx = (ws + G::kTW - 1) / G::kTW, nty = (k.h + G::kTH - 1) / G::kTH;
+    const auto kernel = ws < k.w ? proj_bwd_tiled<DEPTH, CAP, true> : proj_bwd_tiled<DEPTH, CAP, false>;
+    hipLaunchKernelGGL(kernel, dim3(walk_grid(ntx, nty, k.batch, sw)), dim3(256), (tile_lds_bytes<16, CAP>()), k.stream, k.w,
+                       k.h, ntx, nty, k.s1.b, k.s1.c, k.s1.h, k.sd.b, k.sd.h, k.sc.b, k.sc.h, k.flow, k.depth, k.count,
+                       k.fwd_out, k.gout, k.gin1, k.gin2, sw);
+}
+
+// one lane per site.  x0 == 0: every site; x0 > 0: the columns from x0 on (fewer than a wave's)
+template <bool DEPTH>
+static void launch_proj_bwd_direct(const ProjBwdCall &k, int x0 = 0)
+{
+    const int tiles_x = x0 > 0 ? 1 : (k.w + kWave - 1) / kWave, tiles_y = (k.h + 3) / 4;
+    hipLaunchKernelGGL(proj_bwd<DEPTH>, dim3((unsigned)tiles_x * tiles_y * k.batch), dim3(256), 0, k.stream, k.w, k.h, tiles_x,
+                       tiles_y, k.s1.b, k.s1.c, k.s1.h, k.sd.b, k.sd.h, k.sc.b, k.sc.h, k.flow, k.depth, k.count, k.fwd_out,
+                       k.gout, k.gin1, k.gin2, x0);
+}
+
+template <bool DEPTH>
+static int launch_proj_bwd(const ProjBwdCall &k)
+{
+    if (k.w <= 0 || k.h <= 0 || k.batch <= 0) return 0;
+    const bool vec = vec4_ok(k.w, {k.s1.b, k.s1.c, k.s1.h, k.sd.b, k.sd.h, k.sc.b, k.sc.h},
+                             {k.flow, k.depth, k.count, k.fwd_out, k.gout, k.gin1, k.gin2});
     // A width that is not a multiple of four (round 5): the tiled kernel takes the whole quads (sites x < ws), the one-lane-
     // per-site kernel the one to three columns behind them.
-    const int ws = w & ~3;
+    const int ws = k.w & ~3;
     if ((vec || (ws >= 8 && g_proj_variant < 0)) && g_proj_variant != 0) {
-        using G = TileGeom<16>;
-        const int ntx = (ws + G::kTW - 1) / G::kTW, nty = (h + G::kTH - 1) / G::kTH;
-        const int sw = g_tile_walk_sw >= 0 ? g_tile_walk_sw : kDefaultStripe;
-        const unsigned nwg = walk_grid(ntx, nty, batch, sw);
         MEMC_PATH(DEPTH ? "dproj_bwd:tiled" : "proj_bwd:tiled");
-#define MEMC_PROJ_BWD_R(CAP, RAG)                                                                               \
-        hipLaunchKernelGGL((proj_bwd_tiled<DEPTH, CAP, RAG>), dim3(nwg), dim3(256), (tile_lds_bytes<16, CAP>()), stream, w, \
-                           h, ntx, nty, (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)sdb, sdh, (int64_t)scb, sch, flow,   \
-                           depth, count, fwd_out, gout, gin1, gin2, sw)
-#define MEMC_PROJ_BWD(CAP)                                                                                      \
-        do {                                                                                                        \
-            if (ws < w) MEMC_PROJ_BWD_R(CAP, true);                                                                 \
-            else MEMC_PROJ_BWD_R(CAP, false);                                                                       \
-        } while (0)
         // 39 KiB of staged cells instead of 48 -> 4 workgroups per CU: 205 -> 180 us (depth 271 -> 256), same results
 #ifdef MEMC_MEASURE
-        if (g_cap_sel == 0) MEMC_PROJ_BWD(3072);
-        else if (g_cap_sel == 2) MEMC_PROJ_BWD(1984);          // 5 per CU
+        if (g_cap_sel == 0) launch_proj_bwd_tiled<DEPTH, 3072>(k);
+        else if (g_cap_sel == 2) launch_proj_bwd_tiled<DEPTH, 1984>(k);    // 5 per CU
         else
 #endif
-        MEMC_PROJ_BWD(2496);
-#undef MEMC_PROJ_BWD
-#undef MEMC_PROJ_BWD_R
-        if (ws < w) {                          // the ragged row's last columns
-            const int tail_y = (h + 3) / 4;
-            hipLaunchKernelGGL(proj_bwd<DEPTH>, dim3((unsigned)tail_y * batch), dim3(256), 0, stream, w, h, 1, tail_y,
-                               (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)sdb, sdh, (int64_t)scb, sch, flow, depth, count,
-                               fwd_out, gout, gin1, gin2, ws);
-        }
+        launch_proj_bwd_tiled<DEPTH, 2496>(k);
+        if (ws < k.w) launch_proj_bwd_direct<DEPTH>(k, ws);  // the ragged row's last columns
         return launch_status();
     }
-    const int tiles_x = (w + kWave - 1) / kWave, tiles_y = (h + 3) / 4;
-    const unsigned nwg = (unsigned)tiles_x * tiles_y * batch;
     MEMC_PATH(DEPTH ? "dproj_bwd:scalar" : "proj_bwd:scalar");
-    hipLaunchKernelGGL(proj_bwd<DEPTH>, dim3(nwg), dim3(256), 0, stream, w, h, tiles_x, tiles_y,
-                       (int64_t)s1b, (int64_t)s1c, s1h, (int64_t)sdb, sdh, (int64_t)scb, sch, flow, depth, count,
-                       fwd_out, gout, gin1, gin2, 0);
+    launch_proj_bwd_direct<DEPTH>(k);
     return launch_status();
 }
 
@@ -1774,8 +1624,8 @@ extern "C" int FlowProjection_gpu_forward_kernel(
     const float *input1, float *count, float *output)
 {
     (void)nElement; (void)channel; (void)s1w; (void)scc; (void)scw;
-    return launch_proj_fwd<false>((hipStream_t)stream, w, h, batch, fillhole, s1b, s1c, s1h, 0, 0, scb, sch,
-                                  input1, nullptr, count, output);
+    return launch_proj_fwd<false>({(hipStream_t)stream, w, h, batch, fillhole, plane(s1b, s1c, s1h), plane(0, 0, 0),
+                                   plane(scb, 0, sch), input1, nullptr, count, output, nullptr, 0});
 }
 
 extern "C" int FlowProjection_gpu_backward_kernel(
@@ -1785,8 +1635,8 @@ extern "C" int FlowProjection_gpu_backward_kernel(
     const float *input1, const float *count, const float *gradoutput, float *gradinput1)
 {
     (void)nElement; (void)channel; (void)s1w; (void)scc; (void)scw;
-    return launch_proj_bwd<false>((hipStream_t)stream, w, h, batch, s1b, s1c, s1h, 0, 0, scb, sch, input1, nullptr,
-                                  count, nullptr, gradoutput, gradinput1, nullptr);
+    return launch_proj_bwd<false>({(hipStream_t)stream, w, h, batch, plane(s1b, s1c, s1h), plane(0, 0, 0), plane(scb, 0, sch),
+                                   input1, nullptr, count, nullptr, gradoutput, gradinput1, nullptr});
 }
 
 extern "C" int DepthFlowProjection_gpu_forward_kernel(
@@ -1798,8 +1648,8 @@ extern "C" int DepthFlowProjection_gpu_forward_kernel(
     const float *input1, const float *input2, float *count, float *output)
 {
     (void)nElement; (void)channel; (void)s1w; (void)s2c; (void)s2w; (void)scc; (void)scw;
-    return launch_proj_fwd<true>((hipStream_t)stream, w, h, batch, fillhole, s1b, s1c, s1h, s2b, s2h, scb, sch,
-                                 input1, input2, count, output);
+    return launch_proj_fwd<true>({(hipStream_t)stream, w, h, batch, fillhole, plane(s1b, s1c, s1h), plane(s2b, 0, s2h),
+                                  plane(scb, 0, sch), input1, input2, count, output, nullptr, 0});
 }
 
 extern "C" int DepthFlowProjection_gpu_backward_kernel(
@@ -1811,8 +1661,8 @@ extern "C" int DepthFlowProjection_gpu_backward_kernel(
     const float *gradoutput, float *gradinput1, float *gradinput2)
 {
     (void)nElement; (void)channel; (void)s1w; (void)s2c; (void)s2w; (void)scc; (void)scw;
-    return launch_proj_bwd<true>((hipStream_t)stream, w, h, batch, s1b, s1c, s1h, s2b, s2h, scb, sch, input1, input2,
-                                 count, output, gradoutput, gradinput1, gradinput2);
+    return launch_proj_bwd<true>({(hipStream_t)stream, w, h, batch, plane(s1b, s1c, s1h), plane(s2b, 0, s2h), plane(scb, 0, sch),
+                                  input1, input2, count, output, gradoutput, gradinput1, gradinput2});
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1838,8 +1688,8 @@ extern "C" int FlowProjection_gpu_forward_kernel_ws(
 {
     (void)nElement; (void)channel; (void)s1w; (void)scc; (void)scw;
     if (!workspace) return -1;
-    return launch_proj_fwd<false>((hipStream_t)stream, w, h, batch, fillhole, s1b, s1c, s1h, 0, 0, scb, sch,
-                                  input1, nullptr, count, output, workspace, workspace_bytes);
+    return launch_proj_fwd<false>({(hipStream_t)stream, w, h, batch, fillhole, plane(s1b, s1c, s1h), plane(0, 0, 0),
+                                   plane(scb, 0, sch), input1, nullptr, count, output, workspace, workspace_bytes});
 }
 
 extern "C" int DepthFlowProjection_gpu_forward_kernel_ws(
@@ -1852,6 +1702,6 @@ extern "C" int DepthFlowProjection_gpu_forward_kernel_ws(
 {
     (void)nElement; (void)channel; (void)s1w; (void)s2c; (void)s2w; (void)scc; (void)scw;
     if (!workspace) return -1;
-    return launch_proj_fwd<true>((hipStream_t)stream, w, h, batch, fillhole, s1b, s1c, s1h, s2b, s2h, scb, sch,
-                                 input1, input2, count, output, workspace, workspace_bytes);
+    return launch_proj_fwd<true>({(hipStream_t)stream, w, h, batch, fillhole, plane(s1b, s1c, s1h), plane(s2b, 0, s2h),
+                                  plane(scb, 0, sch), input1, input2, count, output, workspace, workspace_bytes});
 }

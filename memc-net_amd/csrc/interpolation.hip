@@ -540,9 +540,7 @@ static int launch_bl_bwd(const BlBwdCall &k)
     g_bwd_cn_allow_c3 = g_cap_sel == 5;                    // arm: RGB through the owner kernels (one chunk, a padded plane)
 #endif
     if (channel != 3 || g_cap_sel == 5) {                  // many channels: fi_bwd_cn.hip (owner-computes)
-        // (the strides came in as the launcher ABI's ints)
-        const int taken = bl_bwd_cn_launch(k.stream, w, h, channel, k.batch, (int)k.s1.b, (int)k.s1.c, k.s1.h, (int)k.s2.b,
-                                           (int)k.s2.c, k.s2.h, k.in1, k.flow, k.gout, k.gin1, k.gin2, g_bl_bwd_direct != 0);
+        const int taken = bl_bwd_cn_launch(k, g_bl_bwd_direct != 0);
         if (taken != 0) {
             MEMC_PATH("bl_bwd:owner");
             return taken > 0 ? 0 : -1;

@@ -15,12 +15,9 @@
 namespace memc {
 // fi_bwd_cn.hip: FilterInterpolation backward for C >= 4 (a ragged last chunk is padded), fs == 4 (tap-gradient kernel +
 // owner-computes image gradient).  1: taken, 0: not taken (the caller falls back to the direct kernel; for this class of channel counts
-// gradinput1 has then been cleared: it is STORED on every path), -1: launch error.  Strides as in the C ABI.
+// gradinput1 has then been cleared: it is STORED on every path), -1: launch error.
 // force_direct: measurement arm -- clear and decline.
-int fi_bwd_cn_launch(hipStream_t stream, int w, int h, int channel, int batch,
-                     int s1b, int s1c, int s1h, int s2b, int s2c, int s2h, int s3b, int s3c, int s3h,
-                     const float *input1, const float *input2, const float *input3, const float *gradoutput,
-                     float *gradinput1, float *gradinput2, float *gradinput3, bool force_direct);
+int fi_bwd_cn_launch(const FiBwdCall<> &call, bool force_direct);
 // the class of channel counts fi_bwd_cn.hip takes -- and for which gradinput1 is stored on every path
 bool fi_bwd_cn_class(int channel, int filter_size);
 #ifdef MEMC_MEASURE
@@ -36,10 +33,7 @@ int fi_bwd_c3_arm_launch(int variant, const FiBwdCall<> &call);
 int fi_bwd_c3_arms_set_trace_buffer(unsigned long long *device_buffer);
 #endif
 // ... and the bilinear warp's backward (Interpolation / InterpolationCh) for the same class of channel counts
-int bl_bwd_cn_launch(hipStream_t stream, int w, int h, int channel, int batch,
-                     int s1b, int s1c, int s1h, int s2b, int s2c, int s2h,
-                     const float *input1, const float *input2, const float *gradoutput,
-                     float *gradinput1, float *gradinput2, bool force_direct);
+int bl_bwd_cn_launch(const BlBwdCall &call, bool force_direct);
 }  // namespace memc
 #endif
 

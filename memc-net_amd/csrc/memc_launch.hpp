@@ -1,7 +1,9 @@
 // memc_launch.hpp -- how the warp launchers hand a call to a kernel (host code only): the strides of a tensor as the
 // kernels take them, and one call descriptor per operator family, filled once at the top of an entry point.  The launch
 // function of a kernel family -- tile count, grid, LDS bytes and the argument list, spelled once -- is a function template
-// beside the kernel (launch_fi_fwd_tiled_fs4 in filter_interpolation.hip, ...).  The descriptors are templates over the
+// beside the kernel (launch_fi_fwd_tiled_fs4 in filter_interpolation.hip, launch_proj_owner5 in flow_projection.hip,
+// launch_fi_bwd_image_owner in fi_bwd_cn.hip, ...).  The measurement build's arms are one function per entry point, in
+// arms/ (fi_fwd_arm_launch, proj_fwd_arm_launch, ...).  The warps' descriptors are templates over the
 // tensors' storage: float in the fp32 library, st_t<...> (memc_lp.hpp) in the half-precision and mixed ones, which fill
 // them from the memc_tensor4s with memc_fi_abi.hpp's fi_fwd_call / fi_blend_fwd_call / fi_bwd_call.
 #pragma once
@@ -67,6 +69,26 @@ struct BlBwdCall {
     int w, h, channel, batch;
     Plane s1, s2;
     const float *in1, *flow, *gout;
+    float *gin1, *gin2;
+};
+
+// FlowProjection / DepthFlowProjection.  s1: the flow, the output / gradoutput, gradinput1; sd: the depth and gradinput2
+// (sd.c is not used; zeros without a depth); sc: the count (sc.c is not used).  ws: the caller's workspace (the _ws entry
+// points) or nullptr: the library's own scratch block.
+struct ProjFwdCall {
+    hipStream_t stream;
+    int w, h, batch, fillhole;
+    Plane s1, sd, sc;
+    const float *flow, *depth;
+    float *count, *out;
+    void *ws;
+    size_t ws_bytes;
+};
+struct ProjBwdCall {
+    hipStream_t stream;
+    int w, h, batch;
+    Plane s1, sd, sc;
+    const float *flow, *depth, *count, *fwd_out, *gout;
     float *gin1, *gin2;
 };
 

@@ -43,6 +43,8 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0, help="the benchmark's flow times this")
     ap.add_argument("--flow", default="smooth", choices=("smooth", "iid"), help="the flow the inputs are generated with")
     ap.add_argument("--shape", default="32x720x1280", help="BxHxW of the main inputs (config 5: 8x2160x3840)")
+    ap.add_argument("--many-channels", type=int, default=64, help="channel count of the *_c64 operators' tensors (8: the smallest "
+                    "count that takes every many-channel kernel)")
     ap.add_argument("--prezero", action="store_true", help="zero-fill the projection's outputs in front of every timed call, outside "
                     "the timed span (what a caller that follows the reference's contract does: FlowProjectionLayer.py:27-28)")
     a = ap.parse_args()
@@ -75,9 +77,9 @@ def main():
     }
     if any(o in a.op.split(",") for o in ("fi_bwd_c64", "interp_bwd_c64", "ctx_img_blend")):
         # the many-channel operators (8 x 64 x 720 x 1280: the context features of config 4's network), allocated on demand
-        m = synth.torch_inputs(dev, 8, 64, H, W, flow_kind="smooth", with_grad=True)
+        m = synth.torch_inputs(dev, 8 if B >= 8 else B, a.many_channels, H, W, flow_kind="smooth", with_grad=True)
         mg1, mg2, mg3 = torch.zeros_like(m["x"]), torch.zeros_like(m["flow"]), torch.zeros_like(m["filt"])
-        mi = {k_: v[:8].contiguous() for k_, v in (("x", x), ("occ", d))}
+        mi = {k_: v[:m["x"].shape[0]].contiguous() for k_, v in (("x", x), ("occ", d))}
         mprev, mio, mco = torch.rand_like(mi["x"]), torch.zeros_like(mi["x"]), torch.zeros_like(m["x"])
         ops["fi_bwd_c64"] = lambda l: l.FilterInterpolationLayer_gpu_backward(m["x"], m["flow"], m["filt"], m["gout"], mg1, mg2, mg3)
         ops["interp_bwd_c64"] = lambda l: l.InterpolationChLayer_gpu_backward(m["x"], m["flow"], m["gout"], mg1, mg2)

@@ -8,8 +8,11 @@ without a GPU) in two trees, the product build and the -DMEMC_MEASURE build, and
     python tools/isa_diff.py BASE [NEW]           # each a directory holding the repository, or a git revision
     python tools/isa_diff.py --only lp_ HEAD      # only the units whose name contains `lp_`
 
-One line per unit: `identical`, or the number of differing lines followed by the kernels whose resource block (VGPRs,
-SGPRs, LDS bytes, scratch bytes, occupancy) changed, old -> new.  Exit status 1 if any unit differs."""
+One line per unit: `identical`; `same functions in another order` where the two files hold the same functions -- body,
+resource block and metadata entry compared by name, the labels' function numbers dropped -- and the same data around
+them (the order of kernels in a code object is the order in which the source first uses each template); or the number
+of differing lines followed by the kernels whose resource block (VGPRs, SGPRs, LDS bytes, scratch bytes, occupancy)
+changed, old -> new.  Exit status 1 if any unit differs in more than the order."""
 import argparse
 import concurrent.futures
 import difflib
@@ -89,9 +92,44 @@ def demangle(names):
         return names
 
 
+_LABEL = re.compile(r"(?<![A-Za-z0-9_])((?:\.L)?(?:BB|JTI|CPI|func_begin|func_end|tmp))\d+")     # .LBB<function number>_<block>, .Lfunc_end<n>
+
+
+def by_function(lines):
+    """({function: its lines, labels without the function number}, {kernel: its metadata entry}, every other line)"""
+    funcs, meta, rest, cur, state = {}, {}, [], None, "text"
+    for l in lines:
+        m = re.search(r"; -- Begin function (\S+)", l)
+        if m:
+            cur, state = funcs.setdefault(m.group(1), []), "func"
+            if rest and rest[-1].startswith("\t.section\t.text." + m.group(1) + ","):       # a template's own section
+                cur.append(rest.pop())
+        elif state == "csdata" and not l.startswith(";"):          # behind the resource comment block: the function is over
+            cur, state = None, "text"
+        elif l.startswith("amdhsa.kernels:"):
+            cur, state = None, "meta"
+        elif state == "meta" and l.startswith("  - "):
+            cur = []
+            meta[len(meta)] = cur
+        elif state == "meta" and not l.startswith("  "):
+            cur, state = None, "text"
+        if cur is None:
+            rest.append(l)
+        else:
+            cur.append(re.sub(r"\s+;", " ;", _LABEL.sub(r"\1#", l)))      # (a comment's column follows the label's width)
+            if state == "func" and ".AMDGPU.csdata" in l:
+                state = "csdata"
+    name = lambda entry: next(l.split()[-1] for l in entry if l.lstrip().startswith(".name:"))
+    return funcs, {name(e): e for e in meta.values()}, rest
+
+
 def compare(a, b):
     if a == b:
         return "identical", []
+    fa, fb = by_function(a), by_function(b)
+    if fa == fb:
+        return "same functions in another order (%d functions, %d kernels: bodies, resource blocks, metadata equal by name)" % (
+            len(fb[0]), len(fb[1])), []
     n = sum(1 for l in difflib.unified_diff(a, b, lineterm="", n=0)
             if l[:1] in "+-" and not l.startswith(("+++", "---")))
     ra, rb = resources(a), resources(b)
@@ -124,7 +162,7 @@ def main():
                     print("%-44s new unit" % label)
                     continue
                 verdict, notes = compare(jobs[label, "a"].result(), jobs[label, "b"].result())
-                differ |= verdict != "identical"
+                differ |= not verdict.startswith(("identical", "same functions in another order"))
                 print("%-44s %s" % (label, verdict))
                 for n in notes:
                     print(n)
