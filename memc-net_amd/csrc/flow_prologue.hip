@@ -29,6 +29,11 @@ namespace memc {
 __device__ __forceinline__ void up_index(int dst, int in, float scale, bool align, int &i0, int &i1, float &l0, float &l1)
 {
     float src = align ? scale * (float)dst : fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.0f);
+    // align_corners: the ROUNDED product is what ATen takes both the index and the weight from.  Left to itself the compiler
+    // contracts `src - i0` below into fma(scale, dst, -i0), a weight off the unrounded product: up to half an ulp of src (3e-5 at
+    // column 625) times the step between two samples away from the torch expression.  (Without align_corners the
+    // products are exact -- scale is 1/4 -- and nothing can differ.)
+    if (align) asm volatile("" : "+v"(src));
     i0 = min((int)src, in - 1);
     i1 = i0 + (i0 < in - 1 ? 1 : 0);
     l1 = src - (float)i0;

@@ -127,3 +127,22 @@ def flow_projection_forward(flow, fillhole=0):
 
 def depth_flow_projection_forward(flow, depth, fillhole=0):
     return _projection_forward("memc_oracle_depth_flow_projection_forward", flow, _prep(depth), fillhole)
+
+
+def flow_projection_backward(flow, count, gout):
+    flow, count, gout = _prep(flow), _prep(count), _prep(gout)
+    g1 = np.zeros(flow.shape, np.float64)
+    B, C, H, W = _dims(flow)
+    _check(lib().memc_oracle_flow_projection_backward(
+        B, C, H, W, _ptr(flow), _str(flow), _ptr(count), _str(count), _ptr(gout), _ptr(g1)), "flow_projection_backward")
+    return g1
+
+
+def depth_flow_projection_backward(flow, depth, count, out, gout):
+    flow, depth, count, out, gout = _prep(flow), _prep(depth), _prep(count), _prep(out), _prep(gout)
+    g1, g2 = np.zeros(flow.shape, np.float64), np.zeros(depth.shape, np.float64)
+    B, C, H, W = _dims(flow)
+    _check(lib().memc_oracle_depth_flow_projection_backward(
+        B, C, H, W, _ptr(flow), _str(flow), _ptr(depth), _str(depth), _ptr(count), _str(count), _ptr(out), _ptr(gout),
+        _ptr(g1), _ptr(g2)), "depth_flow_projection_backward")
+    return g1, g2

@@ -1,4 +1,5 @@
-"""tests/_exact.py -- inputs on which the warps and the projection sums are exact in fp32, whatever the order of the sums.
+"""tests/_exact.py -- inputs on which the warps, the projection sums, the projection backward and the x4 upsampling are exact in
+fp32, whatever the order of the sums.
 
 The grid
     image        k / 16,  k = 0 .. 15            (2^-4)
@@ -6,6 +7,7 @@ The grid
     occlusion    k / 8,   k = -8 .. 8            (2^-3; a block of zeros and a block of negative values, as np_occlusion)
     depth        k / 8,   k = 1 .. 9             (2^-3)
     gradoutput   integers in [-G, G], G = 8
+    context      k / 16,  k = 0 .. 15            (the features warped beside the frame: the image's grid)
     flow         round(4 f) / 4 of an existing generator's flow f (2^-2): a quarter of the sites per axis sit on integer
                  coordinates, so alpha and beta are 0, 1/4, 1/2 or 3/4 and a bilinear weight (1 - alpha)(1 - beta) is a
                  multiple of 2^-4.  Stored in bf16 the flow is clipped to +-63.75, in fp16 to +-511.75 (the largest
@@ -26,6 +28,18 @@ The quantum of each result (the power of two every term and every partial sum is
         forward 2^-4 * 2^-4 = 2^-8, image gradient 1 * 2^-4 = 2^-4, flow gradient 1 * 2^-4 * 2^-2 = 2^-6
     projection sums
         flow 2^-2; with a depth 2^-3 * 2^-2 = 2^-5; counts: integers, or multiples of 2^-3 with a depth
+    projection backward, gradinput1 = -sum_corners gradoutput / count (* depth),
+                         gradinput2 = -sum_corners gradoutput / count * (flow - forward output)
+        The operators' ABI takes count (and the forward's output) as INPUTS.  The premise of these cases: both are
+        SYNTHETIC -- count is +-2^e exactly where the true scatter puts anything (e = 0 .. 4; with a depth -2 .. 4 and a
+        random sign, as real depth counts can be negative) and exactly 0 elsewhere; the forward output is k / 4 in
+        [-64, 64].  Every quotient is then exact: gradoutput / count 2^-4; gradinput1 2^-4, with a depth 2^-7; gradinput2
+        2^-4 * 2^-2 = 2^-6.  A count of 0 is staged as 1 / 0 = inf by the tiled kernel: a read of it by any site
+        comes out as inf or NaN.  Real counts (sums of depths, any value) stay under the 1e-4 tests of
+        tests/test_gpu_parity.py, which remain as they are.
+    x4 upsampling of (mul * flow) / div, flow k / 4 in [-64, 64], (mul, div) = (20, 2) or (6, 3)
+        the scaled flow 2^-1 (exact whether divided or multiplied by the reciprocal); without align_corners the weights
+        are k / 8 per axis: 2^-1 * 2^-6 = 2^-7
 
 Why order cannot matter.  A sum of multiples of 2^-q whose absolute values add up to M has every partial sum, in any
 order and under any grouping, a multiple of 2^-q below M in magnitude: where M * 2^q < 2^24 each of them is a number
@@ -55,7 +69,8 @@ G = 8                         # |gradoutput| <= G
 
 # log2 of one over the quantum, per output
 Q = dict(fi_fwd=11, blend_fwd=14, fi_image=7, fi_taps=8, fi_flow=9, blend_taps=11, blend_flow=12, blend_occ=11,
-         bl_fwd=8, bl_image=4, bl_flow=6, proj=2, dproj=5)
+         bl_fwd=8, bl_image=4, bl_flow=6, proj=2, dproj=5,
+         pb_quot=4, pb_g1=4, dpb_g1=7, dpb_g2=6)
 LIMIT = 2.0 ** 24
 
 CLIP = {"fp32": None, "fp16": 511.75, "bf16": 63.75}
@@ -211,6 +226,142 @@ def projection_inputs(name):
 
 
 PROJECTION = ["row0", "row5", "row8", "pan216", "pan-300", "far"]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# projection backward: the ABI takes count (and the forward's output) as INPUTS, so they are synthetic here
+# ------------------------------------------------------------------------------------------------------------------
+# (B, H, W, flow kind, sigma, seed): the flow is the first draw from default_rng(seed), quantised
+PB_SMALL = [
+    (1, 17, 9, "iid", 2.0, 70),            # the tiled kernel on two quads, one column behind them
+    (2, 9, 7, "iid", 1.5, 71),             # one lane per site: ws = 4 < 8
+    (2, 6, 3, "iid", 1.0, 72),             # one lane per site: below one quad
+    (1, 40, 134, "smooth", 6.0, 73),       # two columns behind the quads
+    (2, 33, 131, "iid", 12.0, 74),         # ragged staging of a clipped box, three columns behind the quads
+]
+PB_SHAPES = ["W50-C3", "W133-C3", "W4-C3"]  # of SHAPES below: the flow only
+
+
+def _pb_id(c):
+    return "%dx%dx%d-%s%g" % c[:5]
+
+
+PB_IDS = TABLE_IDS + PB_SHAPES + [_pb_id(c) for c in PB_SMALL]
+PB_SCALAR = [_pb_id(c) for c in PB_SMALL[1:3]]
+
+
+def pb_flow(name):
+    if name in TABLE_IDS:
+        return table_flow(TABLE[TABLE_IDS.index(name)])
+    if name in PB_SHAPES:
+        return shaped_inputs(*SHAPES[name])[1]
+    B, H, W, kind, sigma, seed = PB_SMALL[[_pb_id(c) for c in PB_SMALL].index(name)]
+    return quantise_flow(synth.np_flow(np.random.default_rng(seed), B, H, W, kind, sigma))
+
+
+def _pb_seed(name):
+    return 4000 + sum(ord(ch) * (i + 1) for i, ch in enumerate(name))
+
+
+def proj_bwd_inputs(name, with_depth):
+    """dict flow, depth, count, fwd_out, gout of a projection-backward case (depth, fwd_out: the depth operator only).
+    count: +-2^e where the true scatter puts anything (e in 0..4; with a depth -2..4 and a random sign: real depth counts
+    can be negative), exactly 0 elsewhere -- the tiled kernel stages 1 / 0 = inf there, which no valid site may read.
+    gradoutput: integers in [-G, G]; on the cells of count 0 its first plane alternates between 0 and a non-zero value
+    (inf * 0 = NaN, inf * g = inf: a wrong read shows either way).  fwd_out: multiples of 1/4 in [-64, 64]."""
+    def make():
+        flow = pb_flow(name)
+        B, _, H, W = flow.shape
+        rng = np.random.default_rng(_pb_seed(name) + (1 if with_depth else 0))
+        hit = project_sums(flow)[1] > 0
+        e = rng.integers(-2 if with_depth else 0, 5, hit.shape)
+        sign = np.where(rng.integers(0, 2, hit.shape) == 1, -1.0, 1.0) if with_depth else 1.0
+        count = np.where(hit, sign * 2.0 ** e, 0.0).astype(np.float32)
+        gout = rng.integers(-G, G + 1, (B, 2, H, W)).astype(np.float32)
+        z = np.flatnonzero(~hit[:, 0])
+        g0 = gout[:, 0].copy().reshape(-1)
+        g0[z[0::2]] = 0.0
+        g0[z[1::2]] = np.where(g0[z[1::2]] == 0, 5.0, g0[z[1::2]])
+        gout[:, 0] = g0.reshape(B, H, W)
+        h = dict(flow=flow, count=count, gout=gout, depth=None, fwd_out=None)
+        if with_depth:
+            h["depth"] = depth(_pb_seed(name), B, H, W)
+            h["fwd_out"] = (rng.integers(-256, 257, (B, 2, H, W)) / 4.0).astype(np.float32)
+        return h
+    return _once(("pb", name, bool(with_depth)), make)
+
+
+def proj_bwd_budget(h):
+    """M per output of the projection backward, from the data: the sums of absolute terms over the four corners of every
+    valid site.  pb_quot: the largest |gradoutput / count| a site reads."""
+    flow, cnt, gout = h["flow"], np.abs(h["count"][:, 0]).astype(np.float64), np.abs(h["gout"]).astype(np.float64)
+    valid, L, T, R, Bm, _x2, _y2 = LP.bl_locate(flow)
+    b = np.arange(flow.shape[0])[:, None, None]
+    corners = [(T, L), (T, R), (Bm, L), (Bm, R)]
+    assert all((cnt[b, yy, xx][valid] > 0).all() for yy, xx in corners), "a valid site reads a count of zero"
+    with np.errstate(divide="ignore", invalid="ignore"):
+        quot = [[np.where(valid, gout[:, k][b, yy, xx] / cnt[b, yy, xx], 0.0) for yy, xx in corners] for k in (0, 1)]
+    if h["depth"] is None:
+        return dict(pb_quot=float(max(q.max() for qs in quot for q in qs)), pb_g1=float(max(sum(qs).max() for qs in quot)))
+    d, fo = h["depth"][:, 0].astype(np.float64), np.abs(h["fwd_out"]).astype(np.float64)
+    g2 = sum(quot[k][i] * (np.abs(flow[:, k]).astype(np.float64) + fo[:, k][b, yy, xx])
+             for k in (0, 1) for i, (yy, xx) in enumerate(corners))
+    return dict(pb_quot=float(max(q.max() for qs in quot for q in qs)), dpb_g1=float(max((sum(qs) * d).max() for qs in quot)),
+                dpb_g2=float(g2.max()))
+
+
+def context(seed, B, C, H, W):
+    """context features on the image's grid, k / 16; from a generator of their own"""
+    return (np.random.default_rng(seed + 5000).integers(0, 16, (B, C, H, W)) / 16.0).astype(np.float32)
+
+
+# context channels per table case: 8 everywhere, 64 on the first case and 4 on the minimum width as well
+CTX_CHANNELS = [[8, 64], [8], [8], [8], [8], [8], [8, 4], [8], [8]]
+
+
+def ctx_inputs(case, C):
+    """(c0, c2): the context features of the two directions of blend_inputs(case)"""
+    def make():
+        B, H, W, _kind, _sigma, seed = case
+        return context(seed, B, C, H, W), context(seed + 100, B, C, H, W)
+    return _once(("ctx", case, C), make)
+
+
+# the layer: the fused route on LAYER_CASE and the two shapes it composes from the separate operators
+CTX_LAYER = ["fused-C8", "composed-C6", "composed-W50"]
+
+
+def ctx_layer_inputs(name):
+    """the ten inputs of FilterInterpolationCtxBlendModule by name, as a dict (blend_inputs' names plus c0, c2)"""
+    def make():
+        if name == "composed-W50":
+            B, _C, H, W, kind, sigma, seed, _taps = SHAPES["W50-C3"]
+            h = dict(parity_blend_inputs((B, 3, H, W, kind, sigma, seed)))
+            C = 8
+        else:
+            B, H, W, _kind, _sigma, seed = LAYER_CASE
+            h = dict(blend_inputs(LAYER_CASE))
+            C = 8 if name == "fused-C8" else 6
+        h["c0"], h["c2"] = context(seed, B, C, H, W), context(seed + 100, B, C, H, W)
+        return h
+    return _once(("ctxlayer", name), make)
+
+
+# x4 upsampling of a scaled flow (flow_prologue.hip): (B, C, h, w) and (mul, div)
+UPSAMPLE_SHAPES = [
+    (1, 2, 3, 323),        # the column loop's second trip, three columns
+    (1, 2, 2, 700),        # three trips, the last one partial
+    (1, 2, 2, 65),         # 128 lanes
+    (2, 2, 5, 13),
+    (1, 1, 1, 1),
+]
+UPSAMPLE_SCALES = [(20.0, 2.0), (6.0, 3.0)]        # a power-of-two divisor (multiplied by its reciprocal) and one that divides
+
+
+def upsample_input(shape):
+    """seeded multiples of 1/4 in [-64, 64]: (mul * f) / div is exact for both scales (5 k / 2 and k / 2), the weights of
+    align_corners = False are multiples of 1/8 per axis: quantum 2^-7, values below 2^10"""
+    return _once(("up", shape), lambda: (np.random.default_rng(6000 + sum(shape)).integers(-256, 257, shape) / 4.0).astype(np.float32))
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,11 @@ of memc_common.hpp; TileGeom<16>, tile_bbox, make_bands<16, true, 3072>, band_re
 memc_fi.hpp; the `done` bookkeeping of fi_fwd_lp_tiled, fi_blend_lp_tiled and fi_bwd_c3_body.inc, which all three share)
 so that a test can state which paths its inputs reach.  tests/test_lowp_path_census.py holds the constants below to the
 header's text and the case table to its conditions; tests/test_gpu_lowp_paths.py runs the table on the GPU.
+
+The last section does the same for the projection backward (flow_projection.hip: launch_proj_bwd's routing, bl_locate<false>,
+tile_region<16, true, 2496>, Region::covers): which sites the tiled kernel gathers from global memory, which tiles clip
+their staged box, which columns go to the one-lane-per-site kernel.  tests/test_exact_inputs.py holds it to the sources'
+text and the cases of tests/_exact.py to their conditions.
 """
 import os
 import sys
@@ -138,3 +143,82 @@ def census(flow):
                 out["max_bands_run"] = max(out["max_bands_run"], run)
                 out["slow"] += int((v & ~done).sum())
     return {k: int(x) for k, x in out.items()}
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the projection backward (flow_projection.hip: launch_proj_bwd, proj_bwd_tiled<DEPTH, 2496, RAG>, proj_bwd<DEPTH>)
+# ------------------------------------------------------------------------------------------------------------------
+PB_CAP = 2496                # the staging budget launch_proj_bwd instantiates (test_exact_inputs.py reads it out of the source)
+
+
+def bl_locate(flow):
+    """bl_locate<false> of memc_common.hpp for every site, in float32: (valid, L, T, R, Bm, x2, y2); invalid sites: L = T = 0"""
+    B, _, H, W = flow.shape
+    fx, fy = flow[:, 0].astype(np.float32), flow[:, 1].astype(np.float32)
+    x2 = np.arange(W, dtype=np.float32)[None, None, :] + fx
+    y2 = np.arange(H, dtype=np.float32)[None, :, None] + fy
+    valid = (x2 >= 0) & (y2 >= 0) & (x2 <= np.float32(W - 1)) & (y2 <= np.float32(H - 1))
+    L = np.where(valid, x2, 0).astype(np.int32)
+    T = np.where(valid, y2, 0).astype(np.int32)
+    return valid, L, T, np.minimum(L + 1, W - 1), np.minimum(T + 1, H - 1), x2, y2
+
+
+def tile_region(cmin, cmax, rmin, rmax, tile_x0, tile_y0, cap=PB_CAP):
+    """tile_region<16, true, cap> of memc_tile.hpp for the box of a tile's valid sites: (x0, y0, w, h, clipped in x, in y)"""
+    x0, y0 = cmin & ~3, rmin
+    w, h = (cmax | 3) + 1 - x0, rmax + 1 - y0
+    clip_x = w > PITCH
+    if clip_x:                                          # clip around the tile centre, keep 4-alignment
+        lo, hi = x0, x0 + w - PITCH
+        x0 = min(max((tile_x0 + TW // 2 - PITCH // 2) & ~3, lo), hi)
+        w = PITCH
+    pitch = (w + 15) & ~15                              # DYN: the narrowest pitch that holds the box buys rows
+    rows = cap // pitch
+    clip_y = h > rows
+    if clip_y:
+        lo, hi = y0, y0 + h - rows
+        y0 = min(max(tile_y0 + TH // 2 - rows // 2, lo), hi)
+        h = rows
+    return x0, y0, w, h, clip_x, clip_y
+
+
+def proj_bwd_route(W):
+    """launch_proj_bwd: ("tiled" | "scalar", ws): whole quads (x < ws = W & ~3) on the tiled kernel and the W & 3 columns
+    behind them on proj_bwd; a ragged width below two quads on proj_bwd alone"""
+    ws = W & ~3
+    return ("tiled" if W % 4 == 0 or ws >= 8 else "scalar"), ws
+
+
+def proj_bwd_census(flow):
+    """Counts over the projection backward of flow [B, 2, H, W].  `uncovered`: valid sites of the tiled kernel whose corners
+    (L..R, T..Bm) lie outside their tile's staged box (Region::covers fails: the gather from global memory); `mask`: those sites."""
+    B, _, H, W = flow.shape
+    route, ws = proj_bwd_route(W)
+    valid, L, T, R, Bm, x2, y2 = bl_locate(flow)
+    out = dict(route=route, ws=ws, sites=int(valid.size), valid=int(valid.sum()), tiles=0, empty=0, clip_x=0, clip_y=0,
+               uncovered=0, tiled_valid=0, tail_valid=0, L_eq_R=int((valid & (L == R)).sum()), T_eq_Bm=int((valid & (T == Bm)).sum()),
+               x2_0=int((valid & (x2 == 0)).sum()), y2_0=int((valid & (y2 == 0)).sum()))
+    mask = np.zeros_like(valid)
+    if route == "scalar":
+        out["tail_valid"] = out["valid"]                # every site on the one-lane-per-site kernel
+        return out, mask
+    out["tail_valid"] = int(valid[:, :, ws:].sum())
+    for b in range(B):
+        for ty in range((H + TH - 1) // TH):
+            for tx in range((ws + TW - 1) // TW):
+                ys, xs = slice(ty * TH, min(ty * TH + TH, H)), slice(tx * TW, min(tx * TW + TW, ws))
+                v = valid[b, ys, xs]
+                out["tiles"] += 1
+                out["tiled_valid"] += int(v.sum())
+                if not v.any():
+                    out["empty"] += 1
+                    continue
+                l, t, r, bm = L[b, ys, xs], T[b, ys, xs], R[b, ys, xs], Bm[b, ys, xs]
+                x0, y0, w, h, cx, cy = tile_region(int(l[v].min()), int(r[v].max()), int(t[v].min()), int(bm[v].max()),
+                                                   tx * TW, ty * TH)
+                out["clip_x"] += cx
+                out["clip_y"] += cy
+                un = v & ~((l >= x0) & (r < x0 + w) & (t >= y0) & (bm < y0 + h))
+                mask[b, ys, xs] = un
+                out["uncovered"] += int(un.sum())
+    return out, mask

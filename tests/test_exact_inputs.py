@@ -5,7 +5,12 @@
   * the sum of absolute terms of every output stays below 2^24 quanta (budget()): no partial sum rounds in ANY order;
   * the quantised flow of a census-table case still reaches the in-kernel paths tests/test_lowp_path_census.py states
     for it, in each of its three storages;
-  * sites sit exactly on the edges of the validity test.
+  * sites sit exactly on the edges of the validity test;
+  * the projection backward on synthetic power-of-two counts: the same three proofs, and a census of the in-kernel
+    branches (uncovered sites, boxes clipped in x and in y, empty tiles, tail columns, the one-lane-per-site route) that
+    _lowp_paths.proj_bwd_census restates from flow_projection.hip and memc_tile.hpp;
+  * the context features beside the frames, and split lanes and slow sites in both directions of a context case;
+  * the x4 upsampling: the scaled flow is exact and torch's CPU result is the same in fp32 and float64.
 These are conditions on the inputs.  If a seed misses one, the seed changes, not the condition.
 """
 import os
@@ -196,3 +201,191 @@ def test_projection_sums(oracle, oracle64, name):
         m = {q: float(np.abs(sa).max())}
         print("%s %s: %s, count up to %g" % (name, q, m, c.max()))
         assert E.holds(m) and c.max() * 8 < E.LIMIT
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# projection backward: synthetic power-of-two counts make every quotient exact
+# ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("with_depth", [False, True], ids=["flow", "depth"])
+@pytest.mark.parametrize("name", E.PB_IDS)
+def test_projection_backward_cases(oracle, oracle64, name, with_depth):
+    h = E.proj_bwd_inputs(name, with_depth)
+    flow, cnt, gout = h["flow"], h["count"], h["gout"]
+    assert np.array_equal(flow * 4, np.round(flow * 4))              # (stored in fp32, unclipped: the operator has no other storage)
+    assert survives(cnt) and survives(gout) and np.abs(gout).max() <= E.G and np.array_equal(gout, np.round(gout))
+    # the premise: a power of two (signed, with a depth) exactly where the true scatter puts anything, exactly 0 elsewhere
+    hit = E.project_sums(flow)[1] > 0
+    assert np.array_equal(cnt != 0, hit)
+    m, e = np.frexp(cnt[hit])
+    assert np.array_equal(np.abs(m), np.full(m.shape, 0.5)) and (-1 if with_depth else 1) <= e.min() and e.max() <= 5
+    if with_depth:                                                   # real depth counts can be negative
+        assert hit.sum() < 8 or ((cnt[hit] > 0).any() and (cnt[hit] < 0).any())
+    else:
+        assert (cnt[hit] > 0).all()
+    zero = ~hit[:, 0]
+    if zero.sum() >= 2:                                              # both kinds of gradoutput on the cells of count 0
+        assert (gout[:, 0][zero] == 0).any() and (gout[:, 0][zero] != 0).any(), name
+    if with_depth:
+        assert survives(h["depth"]) and survives(h["fwd_out"]) and np.abs(h["fwd_out"]).max() <= 64
+        assert np.array_equal(h["fwd_out"] * 4, np.round(h["fwd_out"] * 4))
+        got32 = oracle.depth_flow_projection_backward(flow, h["depth"], cnt, h["fwd_out"], gout)
+        got64 = oracle64.depth_flow_projection_backward(flow, h["depth"], cnt, h["fwd_out"], gout)
+        for a, b, n in zip(got32, got64, ("gradinput1", "gradinput2")):
+            same(a, b, "DepthFlowProjection backward %s %s" % (name, n))
+    else:
+        got64 = (oracle64.flow_projection_backward(flow, cnt, gout),)
+        same(oracle.flow_projection_backward(flow, cnt, gout), got64[0], "FlowProjection backward %s gradinput1" % name)
+    assert all(np.isfinite(g).all() for g in got64), "%s: a valid site read a count of zero" % name
+    m = E.proj_bwd_budget(h)
+    print("%s %s: budget %s" % (name, "depth" if with_depth else "flow", m))
+    assert E.holds(m), (name, m)
+    # the sums of absolute terms bound the results
+    keys = ("dpb_g1", "dpb_g2") if with_depth else ("pb_g1",)
+    assert all(np.abs(g).max() <= m[k] for g, k in zip(got64, keys)), (name, m)
+
+
+def test_projection_backward_constants_are_the_sources():
+    """The census of _lowp_paths.proj_bwd_census restates flow_projection.hip and memc_tile.hpp (kPitch = kTW + 32, kTW = 4 * LX:
+    test_lowp_path_census.test_census_constants_are_the_headers); a change there must change it here too."""
+    import re
+    csrc = os.path.join(LP.ROOT, "memc-net_amd", "csrc")
+    with open(os.path.join(csrc, "flow_projection.hip")) as f:
+        proj = f.read()
+    with open(os.path.join(csrc, "memc_tile.hpp")) as f:
+        tile = f.read()
+
+    def one(text, pattern, what):
+        m = re.findall(pattern, text, re.M)
+        assert len(m) == 1, "expected exactly one `%s` (%s), found %d" % (pattern, what, len(m))
+        return m[0]
+
+    launcher = proj[proj.index("static int launch_proj_bwd(const ProjBwdCall &k)"):]
+    launcher = launcher[:launcher.index("\n}\n")]
+    assert int(one(launcher, r"^\s*launch_proj_bwd_tiled<DEPTH,\s*(\d+)>\(k\);", "the product build's staging budget")) == LP.PB_CAP
+    one(launcher, r"const int ws = k\.w & ~3;", "whole quads")
+    one(launcher, r"if \(\(vec \|\| \(ws >= 8 && g_proj_variant < 0\)\) && g_proj_variant != 0\)", "the routing")
+    one(launcher, r"if \(ws < k\.w\) launch_proj_bwd_direct<DEPTH>\(k, ws\);", "the tail columns' launch")
+    one(tile, r"inline bool vec4_ok\(int w,[^{]*\{\s*\(void\)strides;\s*\(void\)ptrs;\s*return w % 4 == 0;", "vec4_ok: the width alone")
+    kernel = proj[proj.index("void proj_bwd_tiled("):proj.index("MEMC_KNOB_STATIC(g_proj_variant")]
+    assert int(one(kernel, r"constexpr int LX = (\d+);", "lanes per tile row")) == LP.LX
+    one(kernel, r"Region r = tile_region<LX, true, CAP>\(cmin, cmax, rmin, rmax, tile_x0, tile_y0, bb\);", "the dynamic-pitch region")
+    one(kernel, r"st\[j\] = bl_locate<false>\(x \+ j, y, W, H, fx4\[j\], fy4\[j\]\);", "the projection's validity test")
+    one(kernel, r"if \(r\.covers\(s\.L, s\.R, s\.T, s\.Bm\)\)", "the covered branch")
+    one(tile, r"static constexpr int kTH = kThreads / LX;", "the tile height")
+    assert LP.TW + int(one(tile, r"static constexpr int kPitch\s*=\s*kTW\s*\+\s*(\d+)\s*;", "kPitch = kTW + pad")) == LP.PITCH
+    one(tile, r"int x0 = cmin & ~3, w = \(cmax \| 3\) \+ 1 - x0;", "4-alignment of the box")
+    one(tile, r"x0 = min\(max\(\(tile_x0 \+ G::kTW / 2 - G::kPitch / 2\) & ~3, lo\), hi\);", "the clip in x")
+    one(tile, r"const int pitch = DYN \? \(\(w \+ 15\) & ~15\) : G::kPitch;", "the dynamic pitch")
+    one(tile, r"const int rows = DYN \? G::kCapPx / pitch : G::kRows;", "the rows that fit")
+    one(tile, r"y0 = min\(max\(tile_y0 \+ G::kTH / 2 - rows / 2, lo\), hi\);", "the clip in y")
+    one(tile, r"return cmin >= x0 && cmax < x0 \+ w && rmin >= y0 && rmax < y0 \+ h;", "Region::covers")
+    assert (LP.LX, LP.TW, LP.TH, LP.PITCH, LP.PB_CAP // LP.PITCH, LP.PB_CAP // 64) == (16, 64, 16, 96, 26, 39)
+    # tile_region on its own: a box that fits, one clipped in x, one clipped in y
+    assert LP.tile_region(5, 70, 3, 20, 0, 0) == (4, 3, 68, 18, False, False)
+    assert LP.tile_region(0, 255, 0, 9, 64, 0) == (48, 0, 96, 10, True, False)           # centred on the tile: 64 + 32 - 48
+    assert LP.tile_region(64, 127, 0, 63, 64, 16) == (64, 5, 64, 39, False, True)        # pitch 64: 39 rows, 19 above row 24
+    assert LP.proj_bwd_route(7) == ("scalar", 4) and LP.proj_bwd_route(3) == ("scalar", 0)
+    assert LP.proj_bwd_route(4) == ("tiled", 4) and LP.proj_bwd_route(9) == ("tiled", 8) and LP.proj_bwd_route(131) == ("tiled", 128)
+
+
+# what tests/test_gpu_exact.py relies on per projection-backward case: classes of at least five sites (one tile for the tile
+# classes).  Conditions, not measurements: if a case misses one, its seed or sigma changes.
+PB_UNCOVERED = ["1x96x256-smooth25", "2x64x256-iid20", "1x112x320-iid30", "1x200x320-smooth40", "2x100x132-smooth8",
+                "1x20x1280-far", "2x33x131-iid12"]
+PB_CONDITIONS = {
+    "1x96x256-smooth25": dict(clip_x=1, clip_y=1),
+    "2x64x256-iid20": dict(clip_x=32, clip_y=32),                   # every tile
+    "1x20x1280-far": dict(empty=1, clip_x=1),
+    "2x100x132-smooth8": dict(empty=1, clip_y=1),
+    "4x40x40-edges": dict(L_eq_R=5, T_eq_Bm=5, x2_0=5, y2_0=5),
+    "W50-C3": dict(tail_valid=5), "W133-C3": dict(tail_valid=5), "1x17x9-iid2": dict(tail_valid=5),
+    "1x40x134-smooth6": dict(tail_valid=5),
+    "2x33x131-iid12": dict(clip_x=1, clip_y=1, tail_valid=5),
+    "2x9x7-iid1.5": dict(tail_valid=5), "2x6x3-iid1": dict(tail_valid=5),      # (every site on the one-lane-per-site kernel)
+}
+
+
+@pytest.mark.parametrize("name", E.PB_IDS)
+def test_projection_backward_census(name):
+    flow = E.pb_flow(name)
+    c, mask = LP.proj_bwd_census(flow)
+    print("%s: %s" % (name, " ".join("%s=%s" % kv for kv in c.items())))
+    B, _, H, W = flow.shape
+    assert c["route"] == ("scalar" if name in E.PB_SCALAR else "tiled")
+    if c["route"] == "tiled":
+        assert c["tiles"] == B * ((H + 15) // 16) * (((W & ~3) + 63) // 64) and c["tiled_valid"] + c["tail_valid"] == c["valid"]
+        assert (W % 4 != 0) == (name in E.PB_SHAPES[:2] or name in [E._pb_id(k) for k in E.PB_SMALL])
+    assert int(mask.sum()) == c["uncovered"] and c["valid"] >= 5
+    if name in PB_UNCOVERED:
+        assert 5 <= c["uncovered"] < c["tiled_valid"] - 5, c          # both branches of Region::covers
+    else:
+        assert c["uncovered"] == 0, c
+    for k, least in PB_CONDITIONS.get(name, {}).items():
+        assert c[k] >= least, (name, k, c)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the context warp (fi_fwd_ctx_img) and the x4 upsampling
+# ------------------------------------------------------------------------------------------------------------------
+def prove_context(oracle, oracle64, c, flow, filt, what):
+    assert survives(c) and c.min() >= 0
+    w64 = oracle64.filter_interpolation_forward(c, flow, filt)
+    same(oracle.filter_interpolation_forward(c, flow, filt), w64, what)
+    assert E.holds(dict(fi_fwd=float(w64.max()))), what
+
+
+@pytest.mark.parametrize("ci", range(len(E.TABLE)), ids=E.TABLE_IDS)
+def test_context_cases(oracle, oracle64, ci):
+    """the context features of both directions (the frames and their blend: test_blend_directions)"""
+    h = E.blend_inputs(E.TABLE[ci])
+    for C in E.CTX_CHANNELS[ci]:
+        c0, c2 = E.ctx_inputs(E.TABLE[ci], C)
+        assert c0.shape[1] == C and not np.array_equal(c0, c2)
+        prove_context(oracle, oracle64, c0, h["f0"], h["k0"], "%s context 0, C%d" % (E.TABLE_IDS[ci], C))
+        prove_context(oracle, oracle64, c2, h["f1"], h["k1"], "%s context 2, C%d" % (E.TABLE_IDS[ci], C))
+
+
+def test_context_cases_reach_split_lanes_and_slow_sites_in_both_directions():
+    """fi_fwd_ctx_img's blend of ONE element (`blend1`) runs for lanes whose sites are split over bands and for the sites
+    no band covers; its bands are make_bands<16>'s defaults, the census of _lowp_paths"""
+    split = slow = 0
+    for ci, case in enumerate(E.TABLE):
+        c = [LP.census(E.table_flow(case, "fp32", second)) for second in (False, True)]
+        print("%s: split lanes %d / %d, slow sites %d / %d" % (E.TABLE_IDS[ci], c[0]["split_lanes"], c[1]["split_lanes"],
+                                                               c[0]["slow"], c[1]["slow"]))
+        split += min(c[0]["split_lanes"], c[1]["split_lanes"]) >= 5
+        slow += min(c[0]["slow"], c[1]["slow"]) >= 5
+    assert split >= 1 and slow >= 1
+
+
+def test_context_layer_cases(oracle, oracle64):
+    for name in E.CTX_LAYER:
+        h = E.ctx_layer_inputs(name)
+        assert all(survives(h[n]) for n in ("x0", "x2", "c0", "c2", "k0", "k1", "o0", "o1"))
+        w = []
+        for x, c, f, k, o in (("x0", "c0", "f0", "k0", "o0"), ("x2", "c2", "f1", "k1", "o1")):
+            prove_context(oracle, oracle64, h[c], h[f], h[k], "%s %s" % (name, c))
+            w32, w64 = oracle.filter_interpolation_forward(h[x], h[f], h[k]), oracle64.filter_interpolation_forward(h[x], h[f], h[k])
+            same(w32, w64, "%s warp %s" % (name, x))
+            w.append((h[o] * w32, h[o].astype(np.float64) * w64))
+            assert E.holds(dict(blend_fwd=2.0 * float(w64.max())))
+        same(w[0][0] + w[1][0], w[0][1] + w[1][1], name + " blend forward")
+
+
+@pytest.mark.parametrize("mul,div", E.UPSAMPLE_SCALES)
+@pytest.mark.parametrize("shape", E.UPSAMPLE_SHAPES, ids=["%dx%dx%dx%d" % s for s in E.UPSAMPLE_SHAPES])
+def test_upsample_inputs(shape, mul, div):
+    """(mul * f) / div is exact in fp32 in either order, and torch's CPU bilinear x4 (align_corners = False: weights k / 8
+    per axis) returns the same numbers in fp32 and in float64 -- an exact expectation"""
+    import torch.nn.functional as F
+    f = E.upsample_input(shape)
+    assert survives(f) and np.abs(f).max() <= 64 and np.array_equal(f * 4, np.round(f * 4))
+    t = torch.from_numpy(f)
+    s64 = mul * t.double() / div
+    for s32 in (mul * t / div, (mul * t) * (1.0 / div) if div == 2.0 else (mul * t) / div):
+        assert s32.dtype == torch.float32 and torch.equal(s32.double(), s64)
+    assert torch.equal(s64 * 2, torch.round(s64 * 2)) and float(s64.abs().max()) * 2.0 ** 7 < E.LIMIT      # quantum 2^-1 * 2^-6
+    up32 = F.interpolate(mul * t / div, scale_factor=4, mode="bilinear", align_corners=False)
+    up64 = F.interpolate(s64, scale_factor=4, mode="bilinear", align_corners=False)
+    assert up32.dtype == torch.float32 and torch.equal(up32.double(), up64)
+    assert torch.equal(up64 * 128, torch.round(up64 * 128))

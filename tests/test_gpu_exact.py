@@ -1,5 +1,5 @@
-"""Every warp kernel and the projection forward on the exact-arithmetic inputs of tests/_exact.py: bit for bit against the
-fp32 oracle on the same bytes.
+"""Every warp kernel, the context warp, the projection forward and backward and the x4 upsampling on the exact-arithmetic
+inputs of tests/_exact.py: bit for bit against the fp32 oracle on the same bytes.
 
 On those inputs every product and every partial sum is a number of fp32 (tests/test_exact_inputs.py proves it on the CPU,
 with a float64 build of the oracle and a bound on the sum of absolute terms), so the result is the same bits whatever the
@@ -16,11 +16,21 @@ The projection forward divides: count must be exact, cells with count 0 must hol
 derived: the kernels multiply by v_rcp_f32 (<= 1 ulp) or by 1.0f / c (<= 1/2 ulp) and round once more: <= 3 * 2^-24
 relative; 2^-22 leaves a third over that.
 
+The projection backward divides as well, by a count that its ABI takes as an INPUT: the cases hand it synthetic counts,
++-2^e where the true scatter puts anything and exactly 0 elsewhere, so that every quotient is exact and the comparison is
+`torch.equal` like the warps' (the tiled kernel stages 1 / 0 = inf for the empty cells: a wrong read is inf or NaN).
+Which case reaches the uncovered-site branch, a box clipped in x or y, the ragged staging, the tail columns' launch and
+the one-lane-per-site route is counted on the CPU (tests/test_exact_inputs.py::test_projection_backward_census).  Real
+counts stay under the 1e-4 tests of tests/test_gpu_parity.py, which remain as they are.
+The context warp (fi_fwd_ctx_img) records no kernel path: its status is asserted.  The x4 upsampling without
+align_corners has dyadic weights and torch's CPU result in float64 as its expectation; with align_corners it has none and
+runs the same shapes under the rule of test_gpu_parity.test_flow_upsample4.
+
 What this module cannot see: a difference in rounding order (exact inputs have none).  The bit-equality tests between
 the libraries (test_gpu_lowp_paths.py, test_gpu_mx_grad.py) stay for that.  What it sees that they and the 1e-4 rule of
 tests/_parity.py do not: any dropped, doubled or misweighted contribution, down to one part in 2^20 and below, on the
 paths that only atomics reach as well, and sites exactly on the `<=` / `<` edges of the validity test.
-profiles/exact_inputs_observed.md keeps one run's times and what three 2^-20 mutations did to it.
+profiles/exact_inputs_observed.md keeps the runs' times and what six 2^-20 mutations did to it.
 """
 import os
 import sys
@@ -569,3 +579,175 @@ def test_projection_forward(oracle, name):
         rel = float((err / np.maximum(np.abs(q), 1e-300)).max())
         print("%s: worst relative error %.3g * 2^-24 over %d cells" % (what, rel * 2.0 ** 24, q.size))
         assert bool((err <= 2.0 ** -22 * np.abs(q)).all()), (what, rel)
+
+
+# ==================================================================================================================
+# FlowProjection / DepthFlowProjection backward on synthetic power-of-two counts: every quotient is exact
+# ==================================================================================================================
+def want_proj_bwd(oracle, name, with_depth):
+    def make():
+        h = E.proj_bwd_inputs(name, with_depth)
+        if with_depth:
+            return oracle.depth_flow_projection_backward(h["flow"], h["depth"], h["count"], h["fwd_out"], h["gout"])
+        return (oracle.flow_projection_backward(h["flow"], h["count"], h["gout"]),)
+    return once(("pb", name, with_depth), make)
+
+
+def proj_bwd_call(t, with_depth, outs):
+    """the C entry point from pre-filled gradient buffers (every site stores); asserts status and kernel family"""
+    path = "%s:%s" % ("dproj_bwd" if with_depth else "proj_bwd", "scalar" if t["scalar"] else "tiled")
+    if with_depth:
+        assert F32().DepthFlowProjectionLayer_gpu_backward(t["flow"], t["depth"], t["count"], t["fwd_out"], t["gout"], *outs) == 0
+    else:
+        assert F32().FlowProjectionLayer_gpu_backward(t["flow"], t["count"], t["gout"], outs[0]) == 0
+    assert F32().last_kernel_path() == path
+    return outs
+
+
+def proj_bwd_tensors(name, with_depth):
+    h = E.proj_bwd_inputs(name, with_depth)
+    t = {n: D(h[n]) for n in ("flow", "count", "gout") + (("depth", "fwd_out") if with_depth else ())}
+    t["scalar"] = name in E.PB_SCALAR
+    return t
+
+
+@pytest.mark.parametrize("with_depth", [False, True], ids=["flow", "depth"])
+@pytest.mark.parametrize("name", E.PB_IDS)
+def test_projection_backward(oracle, name, with_depth):
+    """which in-kernel branches a case reaches (covered and uncovered sites, boxes clipped in x and y, ragged staging, the
+    tail columns' launch): tests/test_exact_inputs.py::test_projection_backward_census"""
+    t = proj_bwd_tensors(name, with_depth)
+    outs = [filled(t["flow"], NAN)] + ([filled(t["depth"], NAN)] if with_depth else [])
+    proj_bwd_call(t, with_depth, outs)
+    what = "%s backward %s" % ("DepthFlowProjection" if with_depth else "FlowProjection", name)
+    for got, want, n in zip(outs, want_proj_bwd(oracle, name, with_depth), ("gradinput1", "gradinput2")):
+        exact(got, want, "%s %s" % (what, n))
+
+
+def padded7(t, value=None):
+    """t's values (or `value`) in rows 64 floats longer, in a buffer of their own filled with 7.0: (view, buffer)"""
+    B, C, H, W = t.shape
+    buf = torch.full((B, C, H, W + 64), 7.0, device="cuda")
+    view = buf[:, :, :, :W]
+    if value is None:
+        view.copy_(t)
+    else:
+        view.fill_(value)
+    assert not view.is_contiguous() and view.stride(2) == W + 64
+    return view, buf
+
+
+@pytest.mark.parametrize("name", ["2x100x132-smooth8", "2x33x131-iid12"], ids=["whole-quads", "ragged"])
+def test_projection_backward_padded_views_and_run_to_run(oracle, name):
+    """flow, depth, count, the forward's output, gradoutput and the gradients each in a padded buffer of its own (row
+    stride W + 64): the results are the dense ones, twice, and the bytes behind every row of every buffer keep the sentinel"""
+    for with_depth in (False, True):
+        h = E.proj_bwd_inputs(name, with_depth)
+        W = h["flow"].shape[3]
+        names = ("flow", "count", "gout") + (("depth", "fwd_out") if with_depth else ())
+        views = {n: padded7(D(h[n])) for n in names}
+        t = {n: v for n, (v, _buf) in views.items()}
+        t["scalar"] = name in E.PB_SCALAR
+        want = want_proj_bwd(oracle, name, with_depth)
+        runs = []
+        for rnd in range(2):
+            grads = [padded7(t["flow"], NAN)] + ([padded7(t["depth"], NAN)] if with_depth else [])
+            proj_bwd_call(t, with_depth, [g for g, _buf in grads])
+            torch.cuda.synchronize()
+            what = "%s, %s, round %d, padded views" % (name, "depth" if with_depth else "flow", rnd)
+            for (g, _buf), w, n in zip(grads, want, ("gradinput1", "gradinput2")):
+                exact(g, w, "%s: %s" % (what, n))
+            for n, (_v, buf) in list(views.items()) + list(zip(("gradinput1", "gradinput2"), grads)):
+                assert bool((buf[:, :, :, W:] == 7.0).all()), "%s: the bytes behind a row of %s were written" % (what, n)
+            runs.append([g.clone() for g, _buf in grads])
+        assert all(torch.equal(a_, b_) for a_, b_ in zip(*runs))
+        for n in names:                                   # the inputs themselves are untouched as well
+            exact(t[n], h[n], "%s: input %s after the calls" % (name, n))
+
+
+# ==================================================================================================================
+# the frame and its context features in one pass (fi_fwd_ctx_img<BLEND>)
+# ==================================================================================================================
+def ctx_call(img, ctxf, flow, filt, prev=None, oa=None, ob=None):
+    """FilterInterpolationCtxLayer_gpu_forward into NaN-filled outputs; the entry point records no kernel path: its status"""
+    io, co = filled(img, NAN), filled(ctxf, NAN)
+    assert F32().FilterInterpolationCtxLayer_gpu_forward(img, ctxf, flow, filt, prev, oa, ob, io, co) == 0
+    return io, co
+
+
+@pytest.mark.parametrize("ci", range(len(E.TABLE)), ids=E.TABLE_IDS)
+def test_context_warp(oracle, ci):
+    """launch 1 warps frame 0 and its context; launch 2 warps frame 2 and its context and blends the two frames (two
+    products, one sum).  Lanes split over bands and sites no band covers blend one element at a time, out-of-range sites
+    blend the input pixel: tests/test_exact_inputs.py::test_context_cases_reach_split_lanes_and_slow_sites_in_both_directions"""
+    case = E.TABLE[ci]
+    h = E.blend_inputs(case)
+    key = ("table", ci, "fp32")
+    t = {n: D(h[n]) for n in NAMES}
+    for C in E.CTX_CHANNELS[ci]:
+        c0, c2 = E.ctx_inputs(case, C)
+        what = "context warp %s C%d" % (E.TABLE_IDS[ci], C)
+        io, co = ctx_call(t["x0"], D(c0), t["f0"], t["k0"])
+        exact(io, want_direction(oracle, key, h, 0)[4], what + ", launch 1: frame")
+        exact(co, want_fi(oracle, ("ctx", ci, C, 0), c0, h["f0"], h["k0"]), what + ", launch 1: context")
+        io2, co2 = ctx_call(t["x2"], D(c2), t["f1"], t["k1"], io, t["o0"], t["o1"])
+        exact(io2, want_blend(oracle, key, h), what + ", launch 2: blended frame")
+        exact(co2, want_fi(oracle, ("ctx", ci, C, 1), c2, h["f1"], h["k1"]), what + ", launch 2: context")
+
+
+@pytest.mark.parametrize("name", E.CTX_LAYER)
+def test_context_layer(oracle, name):
+    """FilterInterpolationCtxBlendModule: the fused route, and the two shapes it composes from the separate operators"""
+    from my_package.functions.FilterInterpolationCtxBlendLayer import fused_supported
+    from my_package.modules.FilterInterpolationCtxBlendModule import FilterInterpolationCtxBlendModule
+    h = E.ctx_layer_inputs(name)
+    names = ("x0", "x2", "c0", "c2", "f0", "f1", "k0", "k1", "o0", "o1")
+    t = {n: D(h[n]) for n in names}
+    assert fused_supported(t["x0"], t["c0"], t["k0"], t["o0"], *[t[n] for n in ("x2", "c2", "f0", "f1", "k1", "o1")]) == \
+        (name == "fused-C8")
+    with torch.no_grad():
+        blended, c0w, c2w = FilterInterpolationCtxBlendModule()(*[t[n] for n in names])
+    key = ("ctxlayer", name)
+    exact(blended, want_blend(oracle, key, h), name + ": blended frame")
+    exact(c0w, want_fi(oracle, key + (0,), h["c0"], h["f0"], h["k0"]), name + ": context 0")
+    exact(c2w, want_fi(oracle, key + (1,), h["c2"], h["f1"], h["k1"]), name + ": context 2")
+
+
+# ==================================================================================================================
+# x4 upsampling of the scaled flow (flow_upsample4): the column loop's later trips, both divisor branches
+# ==================================================================================================================
+UP_IDS = ["%dx%dx%dx%d" % s for s in E.UPSAMPLE_SHAPES]
+
+
+def upsample_call(f, mul, div, align):
+    B, C, h, w = f.shape
+    out = torch.full((B, C, 4 * h, 4 * w), NAN, device="cuda")
+    assert F32().FlowUpsample4Layer_gpu_forward(f, out, mul, div, align) == 0
+    return out
+
+
+@pytest.mark.parametrize("mul,div", E.UPSAMPLE_SCALES)
+@pytest.mark.parametrize("shape", E.UPSAMPLE_SHAPES, ids=UP_IDS)
+def test_flow_upsample4_exact(shape, mul, div):
+    """align_corners = False: weights k / 8 per axis on an exactly scaled flow -- torch's CPU result in float64 is the
+    expectation (tests/test_exact_inputs.py::test_upsample_inputs: its fp32 result is the same numbers)"""
+    import torch.nn.functional as F
+    f = E.upsample_input(shape)
+    want = once(("up", shape, mul, div), lambda: F.interpolate(mul * torch.from_numpy(f).double() / div, scale_factor=4,
+                                                               mode="bilinear", align_corners=False).numpy())
+    exact(upsample_call(D(f), mul, div, False), want, "flow_upsample4 %s * %g / %g" % (shape, mul, div))
+
+
+@pytest.mark.parametrize("mul,div", E.UPSAMPLE_SCALES)
+@pytest.mark.parametrize("shape", E.UPSAMPLE_SHAPES, ids=UP_IDS)
+def test_flow_upsample4_align_corners(shape, mul, div):
+    """align_corners = True has no dyadic weights: the rule of test_gpu_parity.test_flow_upsample4, against the torch
+    expression the kernel replaces"""
+    import torch.nn.functional as F
+    f = D(E.upsample_input(shape))
+    got = upsample_call(f, mul, div, True)
+    want = F.interpolate(mul * f / div, scale_factor=4, mode="bilinear", align_corners=True)
+    assert got.shape == want.shape
+    err = float((got - want).abs().max())
+    print("flow_upsample4 align_corners %s * %g / %g: max error %g, max |want| %g" % (shape, mul, div, err, float(want.abs().max())))
+    assert err <= 2e-5 * max(1.0, float(want.abs().max())), err
