@@ -5,7 +5,7 @@ The grid
     image        k / 16,  k = 0 .. 15            (2^-4)
     taps         k / 8,   k = 0 .. 7             (2^-3)
     occlusion    k / 8,   k = -8 .. 8            (2^-3; a block of zeros and a block of negative values, as np_occlusion)
-    depth        k / 8,   k = 1 .. 9             (2^-3)
+    depth        k / 8,   k = 1 .. 9             (2^-3); signed_depth: k = -9 .. 9 (the projection forward with hole filling)
     gradoutput   integers in [-G, G], G = 8
     context      k / 16,  k = 0 .. 15            (the features warped beside the frame: the image's grid)
     flow         round(4 f) / 4 of an existing generator's flow f (2^-2): a quarter of the sites per axis sit on integer
@@ -27,7 +27,10 @@ The quantum of each result (the power of two every term and every partial sum is
     bilinear warp (Interpolation, InterpolationCh)
         forward 2^-4 * 2^-4 = 2^-8, image gradient 1 * 2^-4 = 2^-4, flow gradient 1 * 2^-4 * 2^-2 = 2^-6
     projection sums
-        flow 2^-2; with a depth 2^-3 * 2^-2 = 2^-5; counts: integers, or multiples of 2^-3 with a depth
+        flow 2^-2; with a depth 2^-3 * 2^-2 = 2^-5; counts: integers, or multiples of 2^-3 with a depth.  Exact sums make
+        the SIGN of every count certain (signed depths: negative, or exactly zero over a non-zero flow sum), so which
+        cell is a hole, where its walks stop and which stops contribute is the same for every correct implementation:
+        fill_expectation restates the reference's fill in float64, fill_sensitivity says what a walk one cell off would move
     projection backward, gradinput1 = -sum_corners gradoutput / count (* depth),
                          gradinput2 = -sum_corners gradoutput / count * (flow - forward output)
         The operators' ABI takes count (and the forward's output) as INPUTS.  The premise of these cases: both are
@@ -218,6 +221,8 @@ def projection_inputs(name):
             for (y, x, fx, fy) in ((5, 7, 150.0, 0.0), (100, 300, -200.5, 40.25), (160, 20, 30.0, -100.0), (64, 210, 0.0, 25.0),
                                    (40, 180, 35.5, 24.75), (90, 100, -24.0, 3.0), (12, 250, 23.75, -23.75)):
                 f[0, 0, y, x], f[0, 1, y, x] = fx, fy                # ... that (40, 180) -> (215.5, 64.75) lands in
+        elif name in PROJECTION_FILL:
+            f = _fill_case(name)[0]
         else:
             raise ValueError(name)
         B, _, H, W = f.shape
@@ -226,6 +231,114 @@ def projection_inputs(name):
 
 
 PROJECTION = ["row0", "row5", "row8", "pan216", "pan-300", "far"]
+# hole filling: a hole over several 64 x 32 tiles beside an image nothing lands in; walks over 12 tile columns and over 9
+# tile rows (the pending filler's rounds of eight neighbours make a second trip); a ragged width with holes in every tile;
+# a width below 8 (the one-lane-per-site kernels and proj_fillhole); the shape of test_projection_forward_unusual_depths_and_flows
+PROJECTION_FILL = ["2x70x134-patch-empty", "1x12x1280-long-rows", "1x600x8-long-columns", "1x40x70-iid6", "2x9x7-iid2",
+                   "2x45x132-signed"]
+PROJECTION_ALL = PROJECTION + PROJECTION_FILL
+PROJECTION_SIGNED = ["2x70x134-patch-empty", "2x45x132-signed", "1x40x70-iid6", "2x9x7-iid2"]     # run with signed_depth too
+PROJECTION_SENSITIVE = ["far", "2x70x134-patch-empty", "1x12x1280-long-rows"]                        # sensitivity >= 0.9
+PROJECTION_OPS = [(n, op) for n in PROJECTION_ALL for op in ("flow", "depth") + (("signed",) if n in PROJECTION_SIGNED else ())]
+PROJECTION_OP_IDS = ["%s-%s" % k for k in PROJECTION_OPS]
+AWAY = 4000.0                 # a flow that takes every source out of any image here
+
+
+def signed_depth(seed, B, H, W):
+    """k / 8, k = -9 .. 9: depth sums that are negative, or exactly zero over a non-zero flow sum"""
+    rng = np.random.default_rng(seed + 7000)
+    return (rng.integers(-9, 10, (B, 1, H, W)) / 8.0).astype(np.float32)
+
+
+def _fill_case(name):
+    B, H, W = (int(v) for v in name.split("-")[0].split("x"))
+    # (the seeds of the two thin cases: chosen to meet test_exact_inputs.py's sensitivity floors -- every hole of a row or
+    # column of theirs ends at the same stop, so a flow that is flat there hides a walk one cell off from all of them)
+    kind, sigma, seed = {"2x70x134-patch-empty": ("smooth", 4.0, None), "1x12x1280-long-rows": ("smooth", 3.0, 19),
+                         "1x600x8-long-columns": ("iid", 1.5, 12), "1x40x70-iid6": ("iid", 6.0, None),
+                         "2x9x7-iid2": ("iid", 2.0, None), "2x45x132-signed": ("smooth", 5.0, None)}[name]
+    if seed is None:
+        seed = 8000 + sum(ord(ch) * (i + 1) for i, ch in enumerate(name))
+    f = synth.np_flow(np.random.default_rng(seed), B, H, W, kind, sigma)
+    if name == "2x70x134-patch-empty":
+        f[0, :, 20:60, 30:110] = AWAY                                # a 40 x 80 hole over several tiles
+        f[1] = AWAY                                                  # nothing lands in image 1: every cell an unfilled hole
+    elif name == "1x12x1280-long-rows":
+        f[0, :, :, :800] = AWAY
+    elif name == "1x600x8-long-columns":
+        f[0, :, 300:, :] = AWAY
+    elif name == "2x45x132-signed":
+        f[0, :, 3:9, 10:30] = AWAY
+    return f, seed
+
+
+def projection_signed_depth(name):
+    """the signed depth plane of a case of PROJECTION_SIGNED"""
+    B, _, H, W = projection_inputs(name)[0].shape
+    # (seed + 2: the first draw with which 2x70x134-patch-empty meets its sensitivity floor of 0.9 under signed depths too)
+    return _once(("projsigned", name), lambda: signed_depth(_fill_case(name)[1] + 2, B, H, W))
+
+
+def projection_operator(name, op):
+    """(flow, depth or None) of a case under one of the three operators: flow, depth (k / 8 > 0), signed (k / 8, any sign)"""
+    flow, dep = projection_inputs(name)
+    return flow, {"flow": None, "depth": dep, "signed": projection_signed_depth(name) if op == "signed" else None}[op]
+
+
+def fill_expectation(out, count):
+    """oracle/memc_oracle.c project_fillhole on out [B, 2, H, W] (fp32: the averaged output, holes not yet filled) and
+    count [B, 1, H, W], in float64 and without a loop per hole.  A hole is a cell with count <= 0.  Its three walks (left,
+    right, up; there is no downward walk) stop at the nearest cell with count != 0, or at the image border with nothing
+    found; a stop contributes iff its count is > 0 (flags fl, fr, fu; n = fl + fr + fu).  The hole is KEPT when the sum of
+    the three stops' counts (0 where nothing was found) is <= 0 and FILLED otherwise with
+        v = (fl vl + fr vr + fu vu) / n,     and    S = (fl |vl| + fr |vr| + fu |vu|) / n
+    is what an error bound is relative to (|v| can cancel to nothing).  Returns (v, S [B, 2, H, W]; n, filled, kept
+    [B, 1, H, W]); v and S are 0 outside `filled`.  Counts must be exact in float64 (they are on this module's grid)."""
+    o, c = np.asarray(out, dtype=np.float64), np.asarray(count, dtype=np.float64)
+    B, _, H, W = o.shape
+    lo, ro, uo = LP.proj_fill_walks(c)
+    b = np.arange(B)[:, None, None]
+    xs, ys = np.broadcast_to(np.arange(W)[None, None, :], lo.shape), np.broadcast_to(np.arange(H)[None, :, None], lo.shape)
+    stops = ((lo >= 0, ys, np.maximum(lo, 0)), (ro >= 0, ys, np.maximum(ro, 0)), (uo >= 0, np.maximum(uo, 0), xs))
+    cs = [np.where(found, c[:, 0][b, yy, xx], 0.0) for found, yy, xx in stops]
+    flags = [(ck > 0).astype(np.float64) for ck in cs]
+    n = flags[0] + flags[1] + flags[2]
+    hole = c[:, 0] <= 0
+    filled = hole & (cs[0] + cs[1] + cs[2] > 0)
+    v, S = np.zeros_like(o), np.zeros_like(o)
+    for k in (0, 1):
+        vals = [np.where(fl > 0, o[:, k][b, yy, xx], 0.0) for fl, (_found, yy, xx) in zip(flags, stops)]
+        v[:, k] = np.where(filled, sum(vals) / np.maximum(n, 1.0), 0.0)
+        S[:, k] = np.where(filled, sum(np.abs(a) for a in vals) / np.maximum(n, 1.0), 0.0)
+    return v, S, n[:, None], filled[:, None], (hole & ~filled)[:, None]
+
+
+FILL_BOUND = 2.0 ** -21       # the kernels' fill: |got - v| <= FILL_BOUND * S (derived in tests/test_gpu_exact.py)
+
+
+def fill_sensitivity(out, count):
+    """The share of filled holes at which taking, for ONE used neighbour, the next cell outward instead (left of the left
+    stop, right of the right stop, above the upper stop; only where that cell is inside the image and has count > 0) moves a
+    component of the fill by more than 4 * FILL_BOUND * S: what a walk that is one cell off cannot hide behind the bound.
+    (share, filled holes)"""
+    o, c = np.asarray(out, dtype=np.float64), np.asarray(count, dtype=np.float64)[:, 0]
+    B, _, H, W = o.shape
+    _v, S, n, filled, _kept = fill_expectation(out, count)
+    lo, ro, uo = LP.proj_fill_walks(count)
+    b = np.arange(B)[:, None, None]
+    xs, ys = np.broadcast_to(np.arange(W)[None, None, :], lo.shape), np.broadcast_to(np.arange(H)[None, :, None], lo.shape)
+    moved = np.zeros(lo.shape, bool)
+    for pos, dy, dx in ((lo, 0, -1), (ro, 0, 1), (uo, -1, 0)):
+        y0, x0 = (np.maximum(pos, 0), xs) if dy else (ys, np.maximum(pos, 0))
+        y1, x1 = y0 + dy, x0 + dx
+        inside = (pos >= 0) & (y1 >= 0) & (x1 >= 0) & (x1 < W)
+        y1, x1 = np.clip(y1, 0, H - 1), np.clip(x1, 0, W - 1)
+        ok = inside & (c[b, y0, x0] > 0) & (c[b, y1, x1] > 0)
+        for k in (0, 1):
+            delta = np.abs(o[:, k][b, y1, x1] - o[:, k][b, y0, x0]) / np.maximum(n[:, 0], 1.0)
+            moved |= ok & (delta > 4.0 * FILL_BOUND * S[:, k])
+    f = filled[:, 0]
+    return (float((moved & f).sum()) / max(int(f.sum()), 1)), int(f.sum())
 
 
 # ------------------------------------------------------------------------------------------------------------------

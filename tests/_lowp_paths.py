@@ -222,3 +222,76 @@ def proj_bwd_census(flow):
                 mask[b, ys, xs] = un
                 out["uncovered"] += int(un.sum())
     return out, mask
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the projection forward (flow_projection.hip: launch_proj_fwd's routing; proj_fill.hpp: the 64 x kOwnerTH tiles of the
+# owner kernels and of proj_fill_pending, the walks of the hole filling).  tests/test_exact_inputs.py holds the constants
+# to the sources' text and the projection cases of tests/_exact.py to their conditions.
+# ------------------------------------------------------------------------------------------------------------------
+PF_TW, PF_TH = 64, 32        # an owner tile: 64 x kOwnerTH cells
+
+
+def proj_fwd_route(W):
+    """launch_proj_fwd: ("owner" | "scalar", ragged).  vec4_ok is the width alone (memc_tile.hpp: strides and base pointers
+    may be anything), so the owner kernels' ragged-row instantiations serve W >= 8 with W % 4 != 0 and nothing else; a
+    ragged width below 8 takes the one-lane-per-site kernels and proj_fillhole.  Both owner instantiations record `owner`."""
+    if W % 4 == 0:
+        return "owner", False
+    return ("owner", True) if W >= 8 else ("scalar", False)
+
+
+def proj_fill_walks(count):
+    """The three walks of oracle/memc_oracle.c project_fillhole from EVERY cell of count [B, 1, H, W]: the column of the
+    nearest cell with count != 0 to the left and to the right, the row of the nearest one above; -1 where the walk reaches
+    the image border with nothing found.  (lo, ro, uo), each [B, H, W]; cumulative maxima of indices, no loop per cell."""
+    nz = count[:, 0] != 0
+    B, H, W = nz.shape
+    xs, ys = np.arange(W)[None, None, :], np.arange(H)[None, :, None]
+    last = np.maximum.accumulate(np.where(nz, xs, -1), axis=2)            # the last non-zero column <= x
+    lo = np.concatenate([np.full((B, H, 1), -1), last[:, :, :-1]], axis=2)
+    first = np.minimum.accumulate(np.where(nz, xs, W)[:, :, ::-1], axis=2)[:, :, ::-1]   # the first non-zero column >= x
+    ro = np.concatenate([first[:, :, 1:], np.full((B, H, 1), W)], axis=2)
+    ro = np.where(ro == W, -1, ro)
+    above = np.maximum.accumulate(np.where(nz, ys, -1), axis=1)
+    uo = np.concatenate([np.full((B, 1, W), -1), above[:, :-1, :]], axis=1)
+    return lo, ro, uo
+
+
+def proj_fwd_census(s, count):
+    """Counts over the hole filling of the sums s [B, 2, H, W] and count [B, 1, H, W] (float64, exact): per direction the
+    walks of the holes (count <= 0) that end in another 64 x 32 tile, that find nothing, and the most tile borders one
+    crosses; filled holes by the number n of positive neighbours; tiles without a non-zero cell; and what only signed
+    depths reach (negative counts stop a walk, are holes themselves and contribute nothing)."""
+    c = count[:, 0]
+    B, H, W = c.shape
+    lo, ro, uo = proj_fill_walks(count)
+    hole = c <= 0
+    b = np.arange(B)[:, None, None]
+    xs, ys = np.broadcast_to(np.arange(W)[None, None, :], c.shape), np.broadcast_to(np.arange(H)[None, :, None], c.shape)
+    cl = np.where(lo >= 0, c[b, ys, np.maximum(lo, 0)], 0.0)
+    cr = np.where(ro >= 0, c[b, ys, np.maximum(ro, 0)], 0.0)
+    cu = np.where(uo >= 0, c[b, np.maximum(uo, 0), xs], 0.0)
+    n = (cl > 0).astype(int) + (cr > 0) + (cu > 0)
+    filled = hole & (cl + cr + cu > 0)
+    kept = hole & ~filled
+    out = dict(route=proj_fwd_route(W)[0], ragged=proj_fwd_route(W)[1], cells=int(c.size), holes=int(hole.sum()),
+               filled=int(filled.sum()), kept=int(kept.sum()))
+    for k in (1, 2, 3):
+        out["n%d" % k] = int((filled & (n == k)).sum())
+    for name, pos, own, size in (("l", lo, xs, PF_TW), ("r", ro, xs, PF_TW), ("u", uo, ys, PF_TH)):
+        crossed = np.where(hole & (pos >= 0), np.abs(pos // size - own // size), 0)
+        out["other_tile_" + name] = int((crossed > 0).sum())
+        out["nothing_" + name] = int((hole & (pos < 0)).sum())
+        out["borders_" + name] = int(crossed.max())
+    nty, ntx = (H + PF_TH - 1) // PF_TH, (W + PF_TW - 1) // PF_TW
+    pad = np.zeros((B, nty * PF_TH, ntx * PF_TW), bool)
+    pad[:, :H, :W] = c != 0
+    out["tiles"] = B * nty * ntx
+    out["empty_tiles"] = int((~pad.reshape(B, nty, PF_TH, ntx, PF_TW).any(axis=(2, 4))).sum())
+    # what only signed depths reach
+    out["negative"] = int((c < 0).sum())
+    out["zero_count_nonzero_sum"] = int(((c == 0) & (s != 0).any(axis=1)).sum())
+    out["kept_beside_positive"] = int((kept & (n > 0)).sum())
+    out["filled_past_negative"] = int((filled & ((cl < 0) | (cr < 0) | (cu < 0))).sum())
+    return out

@@ -11,10 +11,22 @@ expectation.  Rules, for every test:
   * outputs are pre-filled with NaN (7.0 where the fp32 tests pre-fill what a kernel stores); a gradinput1 that is added
     into starts at 0.5 and must come back as want + 0.5 (a multiple of the quantum as well);
   * last_kernel_path() is asserted for every call that records one (the fp32 blend forward records none).
-The projection forward divides: count must be exact, cells with count 0 must hold exactly 0, elsewhere
-|got - s / c| <= 2^-22 |s / c| for the exact sums s and c (tests/_exact.project_sums, float64 quotient).  The bound is
-derived: the kernels multiply by v_rcp_f32 (<= 1 ulp) or by 1.0f / c (<= 1/2 ulp) and round once more: <= 3 * 2^-24
-relative; 2^-22 leaves a third over that.
+The projection forward divides: count must be exact, cells with count <= 0 must hold float32(s) -- the raw sum nothing
+divided, exactly 0 where nothing landed --, elsewhere |got - s / c| <= 2^-22 |s / c| for the exact sums s and c
+(tests/_exact.project_sums, float64 quotient).  The bound is derived: the kernels multiply by v_rcp_f32 (<= 1 ulp) or by
+1.0f / c (<= 1/2 ulp) and round once more: <= 3 * 2^-24 relative; 2^-22 leaves a third over that.
+With hole filling (fillhole = 1) counts and sums are still exact, so the SIGN of every count is certain -- also under signed
+depths k / 8, k = -9 .. 9, whose sums are negative or cancel to exactly zero over a non-zero flow sum -- and which hole is
+filled from which cells is decided, not ambiguous: a kept hole holds float32(s) bit for bit, a filled one is within
+2^-21 * S of tests/_exact.fill_expectation (oracle/memc_oracle.c project_fillhole in float64) applied to the kernel's own
+output and count, bit-equal to its neighbour where only one contributes; the bound is derived at the test.  The cases
+reach the owner kernels and their in-tile fill, proj_owner_far (a patch of sources that leave the image pulls the motion
+estimate away: such an image is redone there), proj_fill_pending with walks over 12 tile columns and 9 tile rows, the
+ragged-row instantiations and the one-lane-per-site kernels with proj_fillhole; last_kernel_path() comes from the CPU
+restatement of launch_proj_fwd.  The _ws entry points (workspaces full of 0xFF and 0x01), row-padded and misaligned views
+and the two modules are held to the plain entry point's result with `torch.equal`.  What each case reaches is counted in
+tests/test_exact_inputs.py::test_projection_fill_census.  The general path and proj_fillhole_v4 (a stream capture without a
+workspace only) stay under test_gpu_workspace_and_streams.py.
 
 The projection backward divides as well, by a count that its ABI takes as an INPUT: the cases hand it synthetic counts,
 +-2^e where the true scatter puts anything and exactly 0 elsewhere, so that every quotient is exact and the comparison is
@@ -30,7 +42,8 @@ What this module cannot see: a difference in rounding order (exact inputs have n
 the libraries (test_gpu_lowp_paths.py, test_gpu_mx_grad.py) stay for that.  What it sees that they and the 1e-4 rule of
 tests/_parity.py do not: any dropped, doubled or misweighted contribution, down to one part in 2^20 and below, on the
 paths that only atomics reach as well, and sites exactly on the `<=` / `<` edges of the validity test.
-profiles/exact_inputs_observed.md keeps the runs' times and what six 2^-20 mutations did to it.
+profiles/exact_inputs_observed.md keeps the runs' times, what six 2^-20 mutations did to it, and what five mutations of the
+hole filling did.
 """
 import os
 import sys
@@ -550,35 +563,185 @@ def test_layers_backward(oracle, route):
 
 
 # ==================================================================================================================
-# FlowProjection / DepthFlowProjection forward, fillhole = 0
+# FlowProjection / DepthFlowProjection forward
 # ==================================================================================================================
-@pytest.mark.parametrize("name", E.PROJECTION)
-def test_projection_forward(oracle, name):
-    flow, dep = E.projection_inputs(name)
-    B, _, H, W = flow.shape
-    tf = D(flow)
-    for d in (None, dep):
-        s, c = once(("proj", name, d is None), lambda: E.project_sums(flow, d))
-        cnt, out = torch.full((B, 1, H, W), 7.0, device="cuda"), torch.full((B, 2, H, W), 7.0, device="cuda")
-        if d is None:
-            assert F32().FlowProjectionLayer_gpu_forward(tf, cnt, out, 0) == 0
-            assert F32().last_kernel_path() == "proj_fwd:owner"
-            want_cnt = oracle.flow_projection_forward(flow, 0)[1]
-        else:
-            assert F32().DepthFlowProjectionLayer_gpu_forward(tf, D(d), cnt, out, 0) == 0
-            assert F32().last_kernel_path() == "dproj_fwd:owner"
-            want_cnt = oracle.depth_flow_projection_forward(flow, d, 0)[1]
-        what = "%s %s" % ("FlowProjection" if d is None else "DepthFlowProjection", name)
+OP_NAMES = {"flow": "FlowProjection", "depth": "DepthFlowProjection", "signed": "DepthFlowProjection, signed depths"}
+
+
+def proj_ops(name):
+    return [op for n, op in E.PROJECTION_OPS if n == name]
+
+
+def proj_path(W, with_depth):
+    """what last_kernel_path() must say, from the CPU restatement of launch_proj_fwd (test_exact_inputs.py holds it to the source)"""
+    return "%s:%s" % ("dproj_fwd" if with_depth else "proj_fwd", E.LP.proj_fwd_route(W)[0])
+
+
+def proj_call(tf, td, fill, cnt, out, ws=None):
+    """the C entry point (with a workspace: the _ws one); asserts status and kernel path"""
+    args = (tf, cnt, out, fill) if td is None else (tf, td, cnt, out, fill)
+    name = ("FlowProjectionLayer" if td is None else "DepthFlowProjectionLayer") + "_gpu_forward" + ("" if ws is None else "_ws")
+    assert getattr(F32(), name)(*(args if ws is None else args + (ws,))) == 0, name
+    assert F32().last_kernel_path() == proj_path(tf.shape[3], td is not None), name
+    return cnt, out
+
+
+def sevens(B, C, H, W):
+    return torch.full((B, C, H, W), 7.0, device="cuda")
+
+
+def proj_want(oracle, name, op):
+    """(s, c, float32(s), the oracle's count): the exact sums of tests/_exact.project_sums, once per session"""
+    def make():
+        flow, d = E.projection_operator(name, op)
+        s, c = E.project_sums(flow, d)
+        want_cnt = (oracle.flow_projection_forward(flow, 0) if d is None else oracle.depth_flow_projection_forward(flow, d, 0))[1]
         assert np.array_equal(want_cnt, c)
+        return s, c, s.astype(np.float32), want_cnt
+    return once(("proj", name, op), make)
+
+
+def proj_plain(name, op, fill):
+    """(count, output) of the plain C entry point from 7.0-filled dense buffers, once per session; never written again"""
+    def make():
+        flow, d = E.projection_operator(name, op)
+        B, _, H, W = flow.shape
+        cnt, out = proj_call(D(flow), None if d is None else D(d), fill, sevens(B, 1, H, W), sevens(B, 2, H, W))
+        torch.cuda.synchronize()
+        return cnt, out
+    return once(("proj-plain", name, op, fill), make)
+
+
+def check_divided(got, s, c, what):
+    """cells with count > 0: |got - s / c| <= 2^-22 |s / c| (derived in this module's header)"""
+    hit = np.broadcast_to(c > 0, s.shape)
+    q = s[hit] / np.broadcast_to(c, s.shape)[hit]
+    err = np.abs(got.astype(np.float64)[hit] - q)
+    rel = float((err / np.maximum(np.abs(q), 1e-300)).max()) if q.size else 0.0
+    print("%s: worst relative error of a quotient %.3g * 2^-24 over %d cells" % (what, rel * 2.0 ** 24, q.size))
+    assert bool((err <= 2.0 ** -22 * np.abs(q)).all()), (what, rel)
+
+
+@pytest.mark.parametrize("name", E.PROJECTION_ALL)
+def test_projection_forward(oracle, name):
+    """fillhole = 0: the count exact, a cell with count <= 0 holds float32(s) -- the raw sum nothing divided, 0 where nothing
+    landed --, elsewhere the 2^-22 rule against s / c"""
+    for op in proj_ops(name):
+        s, c, s32, want_cnt = proj_want(oracle, name, op)
+        cnt, out = proj_plain(name, op, 0)
+        what = "%s %s" % (OP_NAMES[op], name)
         exact(cnt, want_cnt, what + " count")
-        got = out.cpu().numpy().astype(np.float64)
-        hit = np.broadcast_to(c > 0, s.shape)
-        assert np.array_equal(got[~hit], np.zeros((~hit).sum())), what + ": a cell nothing lands in must hold exactly 0"
-        q = s[hit] / np.broadcast_to(c, s.shape)[hit]
-        err = np.abs(got[hit] - q)
-        rel = float((err / np.maximum(np.abs(q), 1e-300)).max())
-        print("%s: worst relative error %.3g * 2^-24 over %d cells" % (what, rel * 2.0 ** 24, q.size))
-        assert bool((err <= 2.0 ** -22 * np.abs(q)).all()), (what, rel)
+        got = out.cpu().numpy()
+        low = np.broadcast_to(c <= 0, s.shape)
+        assert np.array_equal(got[low], s32[low]), what + ": a cell with count <= 0 must hold the raw sum (0 where nothing lands)"
+        check_divided(got, s, c, what)
+
+
+@pytest.mark.parametrize("name,op", E.PROJECTION_OPS, ids=E.PROJECTION_OP_IDS)
+def test_projection_forward_with_hole_filling(oracle, name, op):
+    """fillhole = 1 through the C entry point, from buffers pre-filled with 7.0.  The count and the cells with count > 0 as
+    without hole filling; a kept hole holds float32(s).  A filled hole is held to tests/_exact.fill_expectation applied to
+    the kernel's OWN output and count -- the expectation takes the kernel's quotients as they are (the cells it reads have
+    count > 0: the fill does not write them), what is tested is the walk and the mix:
+        |got - v| <= 2^-21 * S,   v = (fl vl + fr vr + fu vu) / n,   S = (fl |vl| + fr |vr| + fu |vu|) / n.
+    Derived: at most two additions, each rounding at <= 2^-24 of a partial sum <= n S, and a division or a reciprocal and a
+    multiply at <= 3 * 2^-24 more: 5 * 2^-24 * S; 2^-21 is the next power of two.  Where n = 1 the result is the
+    neighbour's value itself.  Which walks leave their tile, cross how many tiles or find nothing, and what signed depths
+    add: tests/test_exact_inputs.py::test_projection_fill_census; a walk one cell off moves most of the filled holes by more
+    than four times the bound: ::test_projection_fill_sensitivity."""
+    s, c, s32, want_cnt = proj_want(oracle, name, op)
+    cnt, out = proj_plain(name, op, 1)
+    what = "%s %s, hole filling" % (OP_NAMES[op], name)
+    exact(cnt, want_cnt, what + " count")
+    got = out.cpu().numpy()
+    check_divided(got, s, c, what)
+    v, S, n, filled, kept = E.fill_expectation(got, want_cnt)
+    f2, k2 = np.broadcast_to(filled, v.shape), np.broadcast_to(kept, v.shape)
+    assert np.array_equal(got[k2], s32[k2]), "%s: %d kept holes do not hold the raw sum" % (what, int((got[k2] != s32[k2]).sum()))
+    err = np.abs(got.astype(np.float64) - v)
+    worst = float((err[f2] / np.maximum(S[f2], 1e-300)).max()) * 2.0 ** 24 if f2.any() else 0.0
+    bad = f2 & ~(err <= E.FILL_BOUND * S)
+    print("%s: filled holes within %.3g * 2^-24 * S (%d filled, %d kept)" % (what, worst, int(filled.sum()), int(kept.sum())))
+    assert not bad.any(), "%s: %d of %d filled values are off (worst %.3g * 2^-24 * S); first at %s: got %r, want %r" % (
+        what, int(bad.sum()), int(f2.sum()), worst, tuple(int(i) for i in np.argwhere(bad)[0]), float(got[bad][0]), float(v[bad][0]))
+    one = np.broadcast_to(filled & (n == 1), v.shape)
+    assert np.array_equal(got[one].astype(np.float64), v[one]), what + ": one positive neighbour: its value, bit for bit"
+
+
+@pytest.mark.parametrize("name", E.PROJECTION_ALL)
+def test_projection_forward_workspace_entry_points(name):
+    """the _ws entry points on a workspace full of 0xFF and of 0x01 bytes: count and output are the plain entry point's bit
+    for bit (on these inputs no order of the sums can move a bit); where the route is the one-lane-per-site kernels, which
+    use no workspace, the call still returns 0 and gives the same"""
+    for op in proj_ops(name):
+        flow, d = E.projection_operator(name, op)
+        B, _, H, W = flow.shape
+        tf, td = D(flow), None if d is None else D(d)
+        want_cnt, want_out = proj_plain(name, op, 1)
+        nbytes = F32().flow_projection_workspace_bytes(W, H, B, 1, d is not None)
+        assert nbytes > 0 and nbytes % 256 == 0
+        for garbage in (0xFF, 0x01):
+            ws = torch.full((nbytes,), garbage, dtype=torch.uint8, device="cuda")
+            cnt, out = proj_call(tf, td, 1, sevens(B, 1, H, W), sevens(B, 2, H, W), ws)
+            what = "%s %s, workspace of 0x%02X" % (OP_NAMES[op], name, garbage)
+            assert torch.equal(cnt, want_cnt), what + ": count"
+            assert torch.equal(out, want_out), what + ": output"
+
+
+def offset_by_one(t, value=None):
+    """t's values (or `value`) one element into a 7.0-filled buffer of their own: same data, no 16-byte alignment: (view, buffer)"""
+    buf = torch.full((t.numel() + 1,), 7.0, device="cuda")
+    view = buf[1:].view(t.shape)
+    if value is None:
+        view.copy_(t)
+    else:
+        view.fill_(value)
+    assert view.data_ptr() % 16 == 4
+    return view, buf
+
+
+@pytest.mark.parametrize("name", ["2x70x134-patch-empty", "row5"])
+def test_projection_forward_views(name):
+    """fillhole = 1 on row-padded views (row stride W + 64, every tensor in a 7.0-filled buffer of its own), twice, and on
+    views that start one element into their buffers: the dense call's count and output bit for bit, nothing written behind
+    a row or before the first element, the inputs unchanged.  (vec4_ok is the width alone: a misaligned view of a width of
+    whole quads stays on the whole-quad owner kernels, whose quad accesses are unaligned ones.)"""
+    for op in ("flow", "depth"):
+        flow, d = E.projection_operator(name, op)
+        B, _, H, W = flow.shape
+        want_cnt, want_out = proj_plain(name, op, 1)
+        dense = [D(flow)] + ([] if d is None else [D(d)])
+        for kind, mk in (("row-padded", padded7), ("row-padded, second call", padded7), ("offset by one element", offset_by_one)):
+            ins = [mk(a) for a in dense]
+            outs = [mk(sevens(B, 1, H, W), 7.0), mk(sevens(B, 2, H, W), 7.0)]
+            proj_call(ins[0][0], None if d is None else ins[1][0], 1, outs[0][0], outs[1][0])
+            torch.cuda.synchronize()
+            what = "%s %s, %s" % (OP_NAMES[op], name, kind)
+            assert torch.equal(outs[0][0], want_cnt), what + ": count"
+            assert torch.equal(outs[1][0], want_out), what + ": output"
+            for view, buf in ins + outs:
+                if mk is padded7:
+                    assert bool((buf[:, :, :, W:] == 7.0).all()), what + ": the bytes behind a row were written"
+                else:
+                    assert float(buf[0]) == 7.0, what + ": the element before a view was written"
+            for (view, _buf), a in zip(ins, dense):
+                assert torch.equal(view, a), what + ": an input changed"
+
+
+@pytest.mark.parametrize("name", ["2x70x134-patch-empty", "row5"])
+def test_projection_modules(name):
+    """FlowProjectionModule / DepthFlowProjectionModule: requires_grad = False fills the holes (the C entry point's
+    fillhole = 1 result, bit for bit), requires_grad = True does not (its fillhole = 0 result)"""
+    from my_package.modules.DepthFlowProjectionModule import DepthFlowProjectionModule
+    from my_package.modules.FlowProjectionModule import FlowProjectionModule
+    for op, module in (("flow", FlowProjectionModule), ("depth", DepthFlowProjectionModule)):
+        flow, d = E.projection_operator(name, op)
+        args = [D(flow)] + ([] if d is None else [D(d)])
+        with torch.no_grad():
+            got = module(requires_grad=False)(*args)
+        assert torch.equal(got, proj_plain(name, op, 1)[1]), "%s %s: requires_grad = False" % (module.__name__, name)
+        got = module(requires_grad=True)(*args)
+        assert torch.equal(got, proj_plain(name, op, 0)[1]), "%s %s: requires_grad = True" % (module.__name__, name)
 
 
 # ==================================================================================================================
