@@ -12,6 +12,9 @@ numpy alone -- the reference needs scipy.misc.imresize and skimage.color for it,
   * the demo reads frames i and i + 2, interpolates the middle one (pad to multiples of 128, crop: inference.py),
     writes frame i and the rounded result, and scores the result against the real frame i + 1 on the truncated luma
     planes: mean absolute error and PSNR (demo_HD720p.py:75-167).
+
+interpolate_yuv_sequence(..., gpu_io=True) runs the same rule on the device (libmemc_hip_video.so, include/memc_video.h):
+only raw I420 bytes cross the bus.  Off by default; the numpy path is the definition the kernels are tested against.
 """
 import numpy as np
 
@@ -104,11 +107,88 @@ def luma_scores(rec_rgb, gt_rgb):
     return float(np.mean(np.abs(diff))), psnr
 
 
-def interpolate_yuv_sequence(model, in_path, out_path, h, w, device, first=0, last=100, pairs_per_step=1, which=1):
+def scores_from_sums(sum_abs, sum_sq, pixels):
+    """luma_scores' two numbers from the integer sums of |dY| and dY^2 over a plane of `pixels` samples, in float64."""
+    mse = float(int(sum_sq)) / pixels
+    psnr = 100.0 if mse == 0 else float(20.0 * np.log10(255.0 / np.sqrt(mse)))
+    return float(int(sum_abs)) / pixels, psnr
+
+
+def _interpolate_yuv_sequence_gpu(model, in_path, out_path, h, w, device, first, last, pairs_per_step, which):
+    """interpolate_yuv_sequence with the frame I/O on the device (my_package._ext.my_lib_video, include/memc_video.h): per
+    step the raw bytes of frames i, i + 2 and i + 1 of every pair go up, two I420 frames per pair and the integer score
+    sums come down.  Decode writes straight into the padded network input; frame i is encoded from its decoded RGB bytes
+    (what Yuv420Writer does with the reader's frame), the result from the quantised crop of the network's output."""
+    import torch
+    import my_package._ext.my_lib_video as V
+    from .inference import pad_amounts
+    if h % 2 or w % 2:
+        raise ValueError("4:2:0 needs even dimensions, got %dx%d" % (w, h))
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("gpu_io=True needs a CUDA (HIP) device, got %s" % (device,))
+
+    def ok(code, what):
+        if code != 0:
+            raise RuntimeError("%s failed its checks (return code %d)" % (what, code))
+
+    fb = frame_bytes(h, w)
+    left, right, top, bottom = pads = pad_amounts(h, w)
+    hp, wp = h + top + bottom, w + left + right
+    scores = []
+    with open(in_path, "rb") as fin, open(out_path, "wb") as fout:
+        def read(k):
+            fin.seek(k * fb, 0)
+            buf = fin.read(fb)
+            return buf if len(buf) == fb else None
+        index = first
+        while index < last:
+            batch = []
+            while len(batch) < pairs_per_step and index < last:
+                a, b = read(index), read(index + 2)
+                if a is None or b is None:
+                    index = last
+                    break
+                batch.append((index, a, b, read(index + 1)))        # frame i + 1 lies before frame i + 2: it is there
+                index += 2
+            if not batch:
+                break
+            n = len(batch)
+            # [frames i | frames i + 2 | frames i + 1], n of each
+            raw = np.frombuffer(b"".join(t[j] for j in (1, 2, 3) for t in batch), dtype=np.uint8)
+            raw = torch.from_numpy(raw.copy()).to(device).view(3, n, fb)
+            x = torch.empty((2, n, 3, hp, wp), dtype=torch.float32, device=device)
+            rgb_a, rgb_gt, rec = (torch.empty((n, h, w, 3), dtype=torch.uint8, device=device) for _ in range(3))
+            ok(V.i420_decode(raw[0], n, h, w, rgb=rgb_a, planes=x[0], pads=pads), "memc_i420_decode")
+            ok(V.i420_decode(raw[1], n, h, w, planes=x[1], pads=pads), "memc_i420_decode")
+            ok(V.i420_decode(raw[2], n, h, w, rgb=rgb_gt), "memc_i420_decode")
+            with torch.no_grad():
+                frames, _flows, _filters, _occlusions = model(x)
+            ok(V.rgb_quantise(frames[which][:, :, top:top + h, left:left + w], rec), "memc_rgb_quantise")
+            out = torch.empty((n, 2, fb), dtype=torch.uint8, device=device)
+            for k in range(n):                                      # the file's order: frame i, then the result
+                ok(V.i420_encode(rgb_a[k], 1, h, w, out[k, 0]), "memc_i420_encode")
+                ok(V.i420_encode(rec[k], 1, h, w, out[k, 1]), "memc_i420_encode")
+            sums = torch.empty((n, 2), dtype=torch.int64, device=device)
+            work = torch.empty(V.luma_score_workspace_bytes(n, h, w), dtype=torch.uint8, device=device)
+            ok(V.luma_score(rec, rgb_gt, n, h, w, sums, work), "memc_luma_score")
+            fout.write(out.cpu().numpy().tobytes())
+            sums = sums.cpu().numpy().view(np.uint64)
+            for k, t in enumerate(batch):
+                scores.append((t[0] + 1,) + scores_from_sums(sums[k, 0], sums[k, 1], h * w))
+    return scores
+
+
+def interpolate_yuv_sequence(model, in_path, out_path, h, w, device, first=0, last=100, pairs_per_step=1, which=1,
+                             gpu_io=False):
     """The demo loop: for i = first, first + 2, ...: frames i and i + 2 in, the interpolated frame i + 1 out
     (out_path receives frame i, then the interpolated frame), scored against the file's own frame i + 1.
     pairs_per_step > 1 batches that many independent pairs through the network at once (same results: every operator
-    of the path is per frame pair).  Returns the list of (index of the interpolated frame, mean |dY|, PSNR)."""
+    of the path is per frame pair).  Returns the list of (index of the interpolated frame, mean |dY|, PSNR).
+    gpu_io=True (a CUDA device) decodes, quantises, encodes and scores on the device instead of in numpy on the host:
+    the same bytes, but for Y samples whose float64 sum depends on its order (one level at 0.034 % of the RGB triples)."""
+    if gpu_io:
+        return _interpolate_yuv_sequence_gpu(model, in_path, out_path, h, w, device, first, last, pairs_per_step, which)
     import torch
     from .inference import interpolate_pairs
     reader, writer = Yuv420Reader(in_path, h, w, to_rgb=True), Yuv420Writer(out_path, from_rgb=True)

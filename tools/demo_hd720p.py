@@ -4,7 +4,7 @@ frames of a planar YUV 4:2:0 file from its even ones and score them against the 
 
     python tools/demo_hd720p.py --input clip_1280x720.yuv --output clip_interp.yuv [--height 720 --width 1280]
                                 [--model MEMC_Net_star --weights best.pth --align-corners] [--first 0 --last 100]
-                                [--pairs-per-step 4]
+                                [--pairs-per-step 4] [--gpu-io]
 
 Frames i and i + 2 go in (replicate-padded to multiples of 128 like demo_HD720p.py:88-113), the output file receives
 frame i and the interpolated frame i + 1 (demo_HD720p.py:146-149); printed per frame: mean |dY| and PSNR on the 8-bit
@@ -35,6 +35,8 @@ def main(argv=None):
     ap.add_argument("--last", type=int, default=100)
     ap.add_argument("--pairs-per-step", type=int, default=1)
     ap.add_argument("--save-which", type=int, default=1, choices=[0, 1], help="0: blended, 1: rectified (the demos' save_which)")
+    ap.add_argument("--gpu-io", action="store_true",
+                    help="decode, quantise, encode and score on the GPU (libmemc_hip_video.so) instead of in numpy on the host")
     a = ap.parse_args(argv)
 
     import torch
@@ -48,7 +50,7 @@ def main(argv=None):
         net.load_state_dict(state.get("state_dict", state), strict=True)
     net = net.to(dev).eval()
     scores = networks.interpolate_yuv_sequence(net, a.input, a.output, a.height, a.width, dev, first=a.first, last=a.last,
-                                               pairs_per_step=a.pairs_per_step, which=a.save_which)
+                                               pairs_per_step=a.pairs_per_step, which=a.save_which, gpu_io=a.gpu_io)
     for index, err, psnr in scores:
         print("frame %4d  mean|dY| %.4f  PSNR %.3f dB" % (index, err, psnr))
     if scores:
