@@ -26,9 +26,12 @@ Mixed precision (what torch.autocast hands over: float32 frames, float16 / bfloa
 the 4x4 filter and a width that is a multiple of four from 8 on run ONE kernel of libmemc_hip_mx.so on the tensors as they
 are -- the half kernel's float32 arithmetic, the float32 result unrounded -- instead of widening taps, occlusions and flows
 on the host first (112 B per site moved instead of 416).  Where that library declines (a view it cannot read) the call is
-promoted to float32 as before.  The backward widens the saved tensors and runs the float32 backward above, fused
-directions included: the gradients are those of the promoted call, each in its input's dtype.  Any other mix of dtypes is
-promoted by payload_dtype as before.
+promoted to float32 as before.  The backward of a direction whose image needs no gradient is ONE kernel of
+libmemc_hip_mx_blend_grad.so (include/memc_warp_mx_blend_grad.h) on the saved tensors as they are and the float32
+gradoutput: the float32 fused kernel's arithmetic, each gradient rounded once to its input's dtype (108 B per site moved
+instead of about 380).  A direction whose image does need one, or that the library declines, widens its saved tensors and
+runs the float32 backward above, then casts each gradient back.  Either way the gradients are those of the promoted call,
+bit for bit, each in its input's dtype.  Any other mix of dtypes is promoted by payload_dtype as before.
 """
 import torch
 from torch.autograd import Function
@@ -83,9 +86,11 @@ def _direction_backward(x, flow, filt, occ, gradoutput, half=None):
 
 
 def _direction_backward_fused(x, flow, filt, occ, gradoutput):
-    """(flow, tap, occlusion) gradients of ONE direction of the blend whose image wants no gradient, from ONE kernel of
-    libmemc_hip_blend_grad.so on the raw gradoutput (float32; every element of the three is assigned), or None where that
-    kernel does not cover the call (anything but RGB, 16 taps and a width that is a multiple of four from 8 on)."""
+    """(flow, tap, occlusion) gradients of ONE direction of the blend whose image wants no gradient, from ONE kernel on the
+    raw float32 gradoutput (every element of the three is assigned), each in its input's dtype: libmemc_hip_blend_grad.so
+    for float32 tensors, libmemc_hip_mx_blend_grad.so for a float32 image beside half taps and occlusion.  None where that
+    kernel does not cover the call (anything but RGB, 16 taps and a width that is a multiple of four from 8 on; a half
+    view that is not made of 8-byte quads)."""
     g_flow, g_filt, g_occ = torch.empty_like(flow), torch.empty_like(filt), torch.empty_like(occ)
     status = my_lib_blend_grad.FilterInterpolationBlendLayer_gpu_backward(x, flow, filt, occ, gradoutput, g_flow, g_filt,
                                                                           g_occ)
@@ -101,17 +106,24 @@ def _blend_backward(saved, gradoutput, half=None, needs_image_grad=(True, True))
     reference-API entry points (_direction_backward: a forward recomputation + a backward launch).  A float32 direction
     whose image needs none takes the fused kernel (_direction_backward_fused) where it covers the call: its image gradient
     is None.  half: the float16 / bfloat16 tensors that `saved` widens."""
-    input0, input2, flow0, flow1, filter0, filter1, occ0, occ1 = saved
-    grads = []
-    for d, (x, flow, filt, occ) in enumerate(((input0, flow0, filter0, occ0), (input2, flow1, filter1, occ1))):
-        fused = None
-        if half is None and not needs_image_grad[d]:
-            fused = _direction_backward_fused(x, flow, filt, occ, gradoutput)
-        if fused is not None:
-            grads.append((None,) + fused)
-        else:
-            grads.append(_direction_backward(x, flow, filt, occ, gradoutput,
-                                             None if half is None else (half[d], half[2 + d], half[4 + d])))
+    grads = [_direction_grads(saved[d::2], gradoutput, None if half is None else half[d:6:2], needs_image_grad[d])
+             for d in (0, 1)]
+    return _interleave(grads)
+
+
+def _direction_grads(direction, gradoutput, half, needs_image_grad):
+    """(image, flow, tap, occlusion) gradients of ONE float32 direction (x, flow, filt, occ): see _blend_backward"""
+    x, flow, filt, occ = direction
+    fused = None
+    if half is None and not needs_image_grad:
+        fused = _direction_backward_fused(x, flow, filt, occ, gradoutput)
+    if fused is not None:
+        return (None,) + fused
+    return _direction_backward(x, flow, filt, occ, gradoutput, half)
+
+
+def _interleave(grads):
+    """the two directions' (image, flow, tap, occlusion) gradients in the order of the layer's eight inputs"""
     (gx0, gf0, gk0, go0), (gx2, gf1, gk1, go1) = grads
     return gx0, gx2, gf0, gf1, gk0, gk1, go0, go1
 
@@ -167,7 +179,8 @@ def _blend_forward_fp32(args):
 
 class _FilterInterpolationBlendMxFunction(Function):
     """float32 images, float16 / bfloat16 taps and occlusions, flows in float32 or that dtype: forward on libmemc_hip_mx.so
-    (where it declines: promoted to float32, the float32 kernels); backward: the promoted call's, on the widened tensors"""
+    (where it declines: promoted to float32, the float32 kernels); backward: a direction whose image wants no gradient on
+    libmemc_hip_mx_blend_grad.so, on the tensors as they are; any other direction the promoted call's, on widened tensors"""
 
     @staticmethod
     def forward(ctx, input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):
@@ -184,10 +197,18 @@ class _FilterInterpolationBlendMxFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gradoutput):
-        saved = ctx.saved_tensors
-        grads = _blend_backward(tuple(t.float() for t in saved), f32c(gradoutput),       # (contiguous already)
-                                needs_image_grad=ctx.needs_input_grad[:2])
-        return tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, saved))
+        saved, gradoutput = ctx.saved_tensors, f32c(gradoutput)
+        grads = []
+        for d in (0, 1):
+            direction, fused = saved[d::2], None             # (x, flow, filt, occ), contiguous already
+            if not ctx.needs_input_grad[d]:
+                fused = _direction_backward_fused(*direction, gradoutput)      # in the inputs' dtypes
+            if fused is not None:
+                grads.append((None,) + fused)
+            else:                                            # declined, or the image gradient is wanted: promoted
+                g = _direction_grads(tuple(t.float() for t in direction), gradoutput, None, ctx.needs_input_grad[d])
+                grads.append(tuple(None if gi is None else gi.to(t.dtype) for gi, t in zip(g, direction)))
+        return _interleave(grads)
 
 
 def blend_mx_covered(input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):

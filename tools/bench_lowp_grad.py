@@ -15,7 +15,14 @@ the median over the rounds, the spread (max - min over the rounds, relative to t
 The `mixed` group (--only mixed) is the same comparison for the call torch.autocast makes -- a float32 image and a float32
 gradoutput beside half taps: the promoted route (the saved taps and flow cast to float32, _backward_fp32, the tap and flow
 gradients cast back: what _FilterInterpolationMxFunction.backward ran before libmemc_hip_mx_grad.so and still runs where
-that library declines) against the one kernel on the tensors as they are (_backward_mx)."""
+that library declines) against the one kernel on the tensors as they are (_backward_mx).  (--only mixed_bwd: that group
+alone.)
+
+The `mixed_blend` group (--only mixed_blend) is ONE direction of the blend layer's backward for such a call with frames
+that are data: the promoted route (the direction's saved flow, taps and occlusion cast to float32, the float32 fused kernel
+of libmemc_hip_blend_grad.so, the three gradients cast back: what _FilterInterpolationBlendMxFunction.backward ran before
+libmemc_hip_mx_blend_grad.so and still runs where that library declines) against the one kernel on the tensors as they
+are (_direction_backward_fused)."""
 import argparse
 import json
 import math
@@ -39,8 +46,16 @@ ROTATE_BYTES = 1 << 30
 def _sets(shape, n, blend, T, half_flow, seed, mixed=False):
     B, C, H, W = shape
     ft = T if half_flow else torch.float32
-    it = torch.float32 if mixed else T                        # the image and gradoutput of a mixed call stay float32
     out = []
+    it = torch.float32 if mixed else T                        # the image and gradoutput of a mixed call stay float32
+    if blend == "one":                                        # one direction of the mixed blend
+        for i in range(n):
+            t = synth.torch_inputs("cuda", B, C, H, W, flow_kind="smooth", seed=seed + 97 * i)
+            g = torch.Generator("cuda").manual_seed(seed + i)
+            out.append({"x": t["x"], "flow": t["flow"].to(ft), "filt": t["filt"].to(T),
+                        "occ": torch.rand(B, 1, H, W, device="cuda", generator=g).to(T),
+                        "gout": torch.randn(B, C, H, W, device="cuda", generator=g)})
+        return out
     for i in range(n):
         t = synth.torch_inputs("cuda", B, C, H, W, flow_kind="smooth", seed=seed + 97 * i)
         g = torch.Generator("cuda").manual_seed(seed + i)
@@ -91,6 +106,18 @@ def _callers(op, sets, want1):
             grads = FL._backward_mx(s["x"], s["flow"], s["filt"], s["gout"], want1)
             assert grads is not None, "not covered"
             return grads
+    elif op == "mxblend":
+        def widened():                                       # the promoted route of one direction
+            s = pick()
+            saved = (s["x"], s["flow"], s["filt"], s["occ"])
+            grads = BL._direction_grads(tuple(t.float() for t in saved), s["gout"], None, False)
+            return tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, saved))
+
+        def native():
+            s = pick()
+            grads = BL._direction_backward_fused(s["x"], s["flow"], s["filt"], s["occ"], s["gout"])
+            assert grads is not None, "not covered"
+            return grads
     else:
         def _blend(half):
             s = pick()
@@ -112,8 +139,10 @@ def run_case(name, op, shape, T, half_flow, want1, rounds, iters):
     per_set = B * H * W * (2 * C + 16 + 2 * 4) * (2 if op == "blend" else 1) * 2        # half bytes, roughly
     if op == "mx":
         per_set = B * H * W * (2 * C * 4 + 16 * 2 + 2 * 4)    # float32 image and gradoutput, half taps
+    if op == "mxblend":
+        per_set = B * H * W * (2 * C * 4 + 16 * 2 + 2 * 4 + 2)
     n = max(2, math.ceil(ROTATE_BYTES / per_set))
-    sets = _sets(shape, n, op == "blend", T, half_flow, seed=2468, mixed=op == "mx")
+    sets = _sets(shape, n, "one" if op == "mxblend" else op == "blend", T, half_flow, seed=2468, mixed=op == "mx")
     calls = _callers(op, sets, want1)
     times = {"widened": [], "native": []}
     for _ in range(rounds):
@@ -160,6 +189,13 @@ def main():
                                                                    "T" if half_flow else "fp32",
                                                                    "image" if want1 else "noimage"),
                                   "mx", shape, T, half_flow, want1))
+    # the mixed blend group: one direction, frames that are data; the promoted route against libmemc_hip_mx_blend_grad.so
+    for shape in (big, (8, 3, 256, 448)):
+        for tname, T in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
+            for half_flow in (False, True):
+                cases.append(("mixed_blend_bwd %s %s %s flow" % (tname, "x".join(map(str, shape)),
+                                                                 "T" if half_flow else "fp32"),
+                              "mxblend", shape, T, half_flow, False))
     rows = []
     for name, op, shape, T, half_flow, want1 in cases:
         if a.only and a.only not in name:
