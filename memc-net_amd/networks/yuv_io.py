@@ -11,10 +11,12 @@ numpy alone -- the reference needs scipy.misc.imresize and skimage.color for it,
     every second row kept, times 255, truncated to uint8 (:129-148);
   * the demo reads frames i and i + 2, interpolates the middle one (pad to multiples of 128, crop: inference.py),
     writes frame i and the rounded result, and scores the result against the real frame i + 1 on the truncated luma
-    planes: mean absolute error and PSNR (demo_HD720p.py:75-167).
+    planes: mean absolute error, PSNR (demo_HD720p.py:75-167) and, on request, SSIM (:150-190 calls skimage's
+    compare_ssim at its defaults; luma_ssim restates that rule on integer window sums, in numpy alone).
 
 interpolate_yuv_sequence(..., gpu_io=True) runs the same rule on the device (libmemc_hip_video.so, include/memc_video.h):
-only raw I420 bytes cross the bus.  Off by default; the numpy path is the definition the kernels are tested against.
+only raw I420 bytes cross the bus (with ssim=True the third score comes from libmemc_hip_ssim.so, include/memc_ssim.h).
+Off by default; the numpy path is the definition the kernels are tested against.
 """
 import numpy as np
 
@@ -107,6 +109,43 @@ def luma_scores(rec_rgb, gt_rgb):
     return float(np.mean(np.abs(diff))), psnr
 
 
+# skimage's compare_ssim at its defaults on 8-bit planes: 7 x 7 uniform window (49 samples), sample covariance,
+# K1 = 0.01, K2 = 0.03, data range 255; numerator and denominator of its map scaled by 49^2 and 49 * 48 (memc_ssim.h)
+SSIM_C1 = (0.01 * 255) ** 2 * 49 ** 2
+SSIM_C2 = (0.03 * 255) ** 2 * 49 * 48
+
+
+def _box7(p):
+    """int64 [h, w] -> the sums over every 7 x 7 window that lies inside, [h - 6, w - 6], by 2-D cumulative sums"""
+    c = np.zeros((p.shape[0] + 1, p.shape[1] + 1), dtype=np.int64)
+    c[1:, 1:] = p.cumsum(axis=0).cumsum(axis=1)
+    return c[7:, 7:] - c[:-7, 7:] - c[7:, :-7] + c[:-7, :-7]
+
+
+def ssim_from_planes(a, b):
+    """SSIM of two uint8 planes [h, w] as skimage's compare_ssim computes it at its defaults: the mean of the SSIM map over
+    the (h - 6)(w - 6) windows that lie inside the plane.  On bytes the five window sums are exact integers; per window
+        S = ((2 sx sy + c1) (2 Vxy + c2)) / ((sx^2 + sy^2 + c1) (Vxx + Vyy + c2)),  V.. = 49 s.. - s. s.
+    in float64 from the integers (no cancellation: equal planes give exactly 1.0)."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.dtype != np.uint8 or b.dtype != np.uint8 or a.ndim != 2 or a.shape != b.shape:
+        raise ValueError("expected two uint8 planes of one shape, got %s %s and %s %s" % (a.dtype, a.shape, b.dtype, b.shape))
+    if min(a.shape) < 7:
+        raise ValueError("SSIM's 7 x 7 window needs h and w of at least 7, got %dx%d" % (a.shape[1], a.shape[0]))
+    x, y = a.astype(np.int64), b.astype(np.int64)
+    sx, sy, sxx, syy, sxy = _box7(x), _box7(y), _box7(x * x), _box7(y * y), _box7(x * y)
+    vxx, vyy, vxy = 49 * sxx - sx * sx, 49 * syy - sy * sy, 49 * sxy - sx * sy
+    s = ((2 * sx * sy + SSIM_C1) * (2 * vxy + SSIM_C2)) / ((sx * sx + sy * sy + SSIM_C1) * (vxx + vyy + SSIM_C2))
+    return float(np.mean(s))
+
+
+def luma_ssim(rec_rgb, gt_rgb):
+    """The demo's third number for one interpolated frame: SSIM of the truncated 8-bit luma planes, luma_scores' planes."""
+    gy = (rgb_to_yuv(gt_rgb / 255.0)[:, :, 0] * 255.0).astype(np.uint8)
+    ry = (rgb_to_yuv(rec_rgb / 255.0)[:, :, 0] * 255.0).astype(np.uint8)
+    return ssim_from_planes(ry, gy)
+
+
 def scores_from_sums(sum_abs, sum_sq, pixels):
     """luma_scores' two numbers from the integer sums of |dY| and dY^2 over a plane of `pixels` samples, in float64."""
     mse = float(int(sum_sq)) / pixels
@@ -114,13 +153,17 @@ def scores_from_sums(sum_abs, sum_sq, pixels):
     return float(int(sum_abs)) / pixels, psnr
 
 
-def _interpolate_yuv_sequence_gpu(model, in_path, out_path, h, w, device, first, last, pairs_per_step, which):
+def _interpolate_yuv_sequence_gpu(model, in_path, out_path, h, w, device, first, last, pairs_per_step, which, ssim=False):
     """interpolate_yuv_sequence with the frame I/O on the device (my_package._ext.my_lib_video, include/memc_video.h): per
     step the raw bytes of frames i, i + 2 and i + 1 of every pair go up, two I420 frames per pair and the integer score
     sums come down.  Decode writes straight into the padded network input; frame i is encoded from its decoded RGB bytes
-    (what Yuv420Writer does with the reader's frame), the result from the quantised crop of the network's output."""
+    (what Yuv420Writer does with the reader's frame), the result from the quantised crop of the network's output.
+    ssim=True: one memc_ssim_luma_rgb call per step on the result and the real frame, both on the device already; its
+    doubles share the integer sums' buffer and come down with them."""
     import torch
     import my_package._ext.my_lib_video as V
+    if ssim:
+        import my_package._ext.my_lib_ssim as S
     from .inference import pad_amounts
     if h % 2 or w % 2:
         raise ValueError("4:2:0 needs even dimensions, got %dx%d" % (w, h))
@@ -169,26 +212,34 @@ def _interpolate_yuv_sequence_gpu(model, in_path, out_path, h, w, device, first,
             for k in range(n):                                      # the file's order: frame i, then the result
                 ok(V.i420_encode(rgb_a[k], 1, h, w, out[k, 0]), "memc_i420_encode")
                 ok(V.i420_encode(rec[k], 1, h, w, out[k, 1]), "memc_i420_encode")
-            sums = torch.empty((n, 2), dtype=torch.int64, device=device)
+            down = torch.empty(n * (3 if ssim else 2), dtype=torch.int64, device=device)   # [n, 2] sums | n doubles
+            sums = down[:2 * n].view(n, 2)
             work = torch.empty(V.luma_score_workspace_bytes(n, h, w), dtype=torch.uint8, device=device)
             ok(V.luma_score(rec, rgb_gt, n, h, w, sums, work), "memc_luma_score")
+            if ssim:
+                work = torch.empty(S.ssim_workspace_bytes(n, h, w), dtype=torch.uint8, device=device)
+                ok(S.ssim_luma_rgb(rec, rgb_gt, n, h, w, down[2 * n:].view(torch.float64), work), "memc_ssim_luma_rgb")
             fout.write(out.cpu().numpy().tobytes())
-            sums = sums.cpu().numpy().view(np.uint64)
+            down = down.cpu().numpy()
+            sums = down[:2 * n].reshape(n, 2).view(np.uint64)
             for k, t in enumerate(batch):
-                scores.append((t[0] + 1,) + scores_from_sums(sums[k, 0], sums[k, 1], h * w))
+                score = (t[0] + 1,) + scores_from_sums(sums[k, 0], sums[k, 1], h * w)
+                scores.append(score + (float(down[2 * n + k:2 * n + k + 1].view(np.float64)[0]),) if ssim else score)
     return scores
 
 
 def interpolate_yuv_sequence(model, in_path, out_path, h, w, device, first=0, last=100, pairs_per_step=1, which=1,
-                             gpu_io=False):
+                             gpu_io=False, ssim=False):
     """The demo loop: for i = first, first + 2, ...: frames i and i + 2 in, the interpolated frame i + 1 out
     (out_path receives frame i, then the interpolated frame), scored against the file's own frame i + 1.
     pairs_per_step > 1 batches that many independent pairs through the network at once (same results: every operator
-    of the path is per frame pair).  Returns the list of (index of the interpolated frame, mean |dY|, PSNR).
+    of the path is per frame pair).  Returns the list of (index of the interpolated frame, mean |dY|, PSNR); with
+    ssim=True every tuple gains a fourth element, the SSIM of the two luma planes (luma_ssim).
     gpu_io=True (a CUDA device) decodes, quantises, encodes and scores on the device instead of in numpy on the host:
     the same bytes, but for Y samples whose float64 sum depends on its order (one level at 0.034 % of the RGB triples)."""
     if gpu_io:
-        return _interpolate_yuv_sequence_gpu(model, in_path, out_path, h, w, device, first, last, pairs_per_step, which)
+        return _interpolate_yuv_sequence_gpu(model, in_path, out_path, h, w, device, first, last, pairs_per_step, which,
+                                             ssim)
     import torch
     from .inference import interpolate_pairs
     reader, writer = Yuv420Reader(in_path, h, w, to_rgb=True), Yuv420Writer(out_path, from_rgb=True)
@@ -219,7 +270,7 @@ def interpolate_yuv_sequence(model, in_path, out_path, h, w, device, first=0, la
                 writer.write(rec)
                 gt, ok = reader.read(i + 1)
                 if ok:
-                    scores.append((i + 1,) + luma_scores(rec, gt))
+                    scores.append((i + 1,) + luma_scores(rec, gt) + ((luma_ssim(rec, gt),) if ssim else ()))
     finally:
         reader.close()
         writer.close()

@@ -4,11 +4,13 @@ frames of a planar YUV 4:2:0 file from its even ones and score them against the 
 
     python tools/demo_hd720p.py --input clip_1280x720.yuv --output clip_interp.yuv [--height 720 --width 1280]
                                 [--model MEMC_Net_star --weights best.pth --align-corners] [--first 0 --last 100]
-                                [--pairs-per-step 4] [--gpu-io]
+                                [--pairs-per-step 4] [--gpu-io] [--ssim]
 
 Frames i and i + 2 go in (replicate-padded to multiples of 128 like demo_HD720p.py:88-113), the output file receives
 frame i and the interpolated frame i + 1 (demo_HD720p.py:146-149); printed per frame: mean |dY| and PSNR on the 8-bit
-luma planes (:150-167).  Without --weights the network runs on its random initialisation (plumbing check only).
+luma planes (:150-167).  --ssim adds the SSIM of the two luma planes (:150-190: skimage's compare_ssim at its defaults) and
+writes <output>_psnr_Y.txt and <output>_ssim_Y.txt, one value per line.  Without --weights the network runs on its random
+initialisation (plumbing check only).
 Needs a GPU: the operators have no CPU path.
 """
 import argparse
@@ -37,6 +39,9 @@ def main(argv=None):
     ap.add_argument("--save-which", type=int, default=1, choices=[0, 1], help="0: blended, 1: rectified (the demos' save_which)")
     ap.add_argument("--gpu-io", action="store_true",
                     help="decode, quantise, encode and score on the GPU (libmemc_hip_video.so) instead of in numpy on the host")
+    ap.add_argument("--ssim", action="store_true",
+                    help="also score SSIM on the luma planes (with --gpu-io: libmemc_hip_ssim.so) and write <output>_psnr_Y.txt "
+                         "and <output>_ssim_Y.txt")
     a = ap.parse_args(argv)
 
     import torch
@@ -50,12 +55,18 @@ def main(argv=None):
         net.load_state_dict(state.get("state_dict", state), strict=True)
     net = net.to(dev).eval()
     scores = networks.interpolate_yuv_sequence(net, a.input, a.output, a.height, a.width, dev, first=a.first, last=a.last,
-                                               pairs_per_step=a.pairs_per_step, which=a.save_which, gpu_io=a.gpu_io)
-    for index, err, psnr in scores:
-        print("frame %4d  mean|dY| %.4f  PSNR %.3f dB" % (index, err, psnr))
+                                               pairs_per_step=a.pairs_per_step, which=a.save_which, gpu_io=a.gpu_io,
+                                               **(dict(ssim=True) if a.ssim else {}))
+    for s in scores:
+        print("frame %4d  mean|dY| %.4f  PSNR %.3f dB" % s[:3] + ("  SSIM %.6f" % s[3] if a.ssim else ""))
     if scores:
         print("average over %d interpolated frames: mean|dY| %.4f  PSNR %.3f dB" % (
-            len(scores), sum(s[1] for s in scores) / len(scores), sum(s[2] for s in scores) / len(scores)))
+            len(scores), sum(s[1] for s in scores) / len(scores), sum(s[2] for s in scores) / len(scores))
+            + ("  SSIM %.6f" % (sum(s[3] for s in scores) / len(scores)) if a.ssim else ""))
+    if a.ssim:
+        for suffix, column in (("_psnr_Y.txt", 2), ("_ssim_Y.txt", 3)):
+            with open(a.output + suffix, "w") as f:
+                f.write("".join("%r\n" % s[column] for s in scores))
 
 
 if __name__ == "__main__":
