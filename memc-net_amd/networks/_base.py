@@ -28,6 +28,10 @@ except ImportError:
 from ._blocks import FlowEstimator, run_unet, unet_head, unet_trunk
 
 
+def _all_float32(*tensors):
+    return all(t.dtype == torch.float32 for t in tensors)
+
+
 class MEMCNetBase(nn.Module):
     div_flow = 20                                      # FlowNetS predicts flow / 20
 
@@ -85,7 +89,8 @@ class MEMCNetBase(nn.Module):
     def _bidirectional_flow(self, pair):
         """quarter-resolution single-direction flow -> full resolution, halved for the middle frame"""
         flow = self.flownets(pair)
-        if self.fused_upsample and FlowUpsample4Module is not None and flow.is_cuda:
+        # (the fused layer is float32-only: a half flow -- a cast model, autocast -- takes the torch expression)
+        if self.fused_upsample and FlowUpsample4Module is not None and flow.is_cuda and _all_float32(flow):
             return FlowUpsample4Module(self.div_flow, 2.0, self.align_corners)(flow)      # (div_flow * flow) / 2.0, x4
         return F.interpolate(self.div_flow * flow / 2.0, scale_factor=4, mode="bilinear", align_corners=self.align_corners)
 
@@ -125,8 +130,15 @@ class MEMCNetBase(nn.Module):
                                                        self.initScaleNets_occlusion2, both)]
 
         warp = FilterInterpolationModule()
-        feats = self._context_features(frame0, frame2) if self.fused_context else None
-        if feats is not None and FilterInterpolationCtxBlendModule is not None:
+        # the context + blend layer is float32-only: with a half or mixed call (a cast model, autocast, where the heads
+        # return half tensors beside float32 frames) the switch is a no-op and the path below, which handles both, runs.
+        # Every tensor but the features is known before ctxNet runs, so a declined switch costs nothing
+        fused_context = (self.fused_context and FilterInterpolationCtxBlendModule is not None
+                         and _all_float32(frame0, frame2, *flows, *filters, *occlusions))
+        feats = self._context_features(frame0, frame2) if fused_context else None
+        if feats is not None and not _all_float32(*feats):
+            feats = None                                # (a ctxNet of another dtype than the frames)
+        if feats is not None:
             # frames and context features ride the same flow + taps: one launch per direction, blend included
             blended, ctx0, ctx2 = FilterInterpolationCtxBlendModule()(
                 frame0, frame2, feats[0], feats[1], flows[0], flows[1], filters[0], filters[1], occlusions[0],
