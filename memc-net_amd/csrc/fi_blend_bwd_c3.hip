@@ -17,7 +17,8 @@
 // bands): tests/_lowp_paths.py::census describes this kernel's in-kernel paths too.
 // Every element of the three outputs is assigned; the results are a pure function of the inputs.
 // The kernel's body (fi_blend_bwd_c3_body.inc) and its three per-site paths (memc_fi_blend_bwd_c3.hpp) are written over the
-// storage of the tensors: mx_fi_blend_bwd_c3.hip runs them on half taps and occlusions; here every tag is F32.
+// storage of the tensors: mx_fi_blend_bwd_c3.hip runs them on half taps and occlusions, lp_fi_blend_bwd_c3.hip on a half
+// image as well; here every tag is F32.
 #include "memc_common.hpp"
 #include "memc_fi_blend_bwd_c3.hpp"
 #include "memc_fi_abi.hpp"
@@ -38,8 +39,10 @@ __global__ __launch_bounds__(NT, 2) void fi_blend_bwd_c3(
     const float *__restrict__ occ, const float *__restrict__ gout, float *__restrict__ gflow,
     float *__restrict__ gfilt, float *__restrict__ gocc)
 {
+    using I = F32;
     using T = F32;
     using FT = F32;
+    using GT = F32;
 #include "fi_blend_bwd_c3_body.inc"
 }
 

@@ -3,11 +3,13 @@
 // tensors (memc_lp.hpp: F32, F16, BF16).
 //   fi_blend_bwd_c3.hip      fi_blend_bwd_c3: fp32 (libmemc_hip_blend_grad.so), the description of the algorithm;
 //   mx_fi_blend_bwd_c3.hip   fi_blend_bwd_c3_mx: fp32 image and gradoutput, fp16 / bf16 taps and occlusion, fp32 or half flow
-//                            (libmemc_hip_mx_blend_grad.so).
-// T: the storage of the taps, the occlusion and their gradients; FT: that of the flow and its gradient.  The image and
-// gradoutput are fp32 in both.  Loads widen exactly, each stored gradient is rounded once: the LDS image and the arithmetic
-// are the same for every storage, and the F32 instantiations are the code the fp32 unit had before the storage was made a
-// parameter (tools/isa_diff.py).
+//                            (libmemc_hip_mx_blend_grad.so);
+//   lp_fi_blend_bwd_c3.hip   fi_blend_bwd_c3_lp: fp16 / bf16 image, taps and occlusion, fp32 or half flow and gradoutput
+//                            (libmemc_hip_lp_blend_grad.so).
+// T: the storage of the taps, the occlusion and their gradients; FT: that of the flow and its gradient; I: the image's;
+// GT: gradoutput's (I = GT = F32 in the first two).  Loads widen exactly, each stored gradient is rounded once: the LDS
+// image and the arithmetic are the same for every storage, and the fp32 and mixed instantiations are the code their units
+// had before the image's and gradoutput's storage were made parameters (tools/isa_diff.py).
 #pragma once
 
 #include "memc_common.hpp"
@@ -17,16 +19,16 @@
 namespace memc {
 
 // One direction of the blend's backward.  s1: the image and gradoutput; s2: the flow and its gradient; s3: the taps and
-// their gradient; s4: the occlusion and its gradient (one channel: no channel stride).  T / FT: element types.
-template <class T = float, class FT = float>
+// their gradient; s4: the occlusion and its gradient (one channel: no channel stride).  T / FT / IT / GT: element types.
+template <class T = float, class FT = float, class IT = float, class GT = float>
 struct FiBlendBwdCall {
     hipStream_t stream;
     int w, h, batch;
     Plane s1, s2, s3, s4;
-    const float *in1;
+    const IT *in1;
     const FT *flow;
     const T *filt, *occ;
-    const float *gout;
+    const GT *gout;
     FT *gflow;
     T *gfilt, *gocc;
 };
@@ -78,20 +80,21 @@ __device__ __forceinline__ void fi_blend_bwd_phase1(const Region &r, unsigned fa
 
 // The three gradients of ONE site straight from global memory (fi_bwd_site_taps of memc_fi.hpp with the occlusion): mixed
 // quads and sites that no band covers.  An invalid site keeps what fi_blend_bwd_store_invalid stored.  A macro body,
-// expanded in the fp32 unit's named function and in the mixed template (see memc_fi.hpp on why not a forwarding call);
-// halves are read through widen_f32, so that the compiler sees fp32 operands as in the fp32 function.
-#define MEMC_FI_BLEND_BWD_SITE_BODY(T, FT)                                                                            \
+// expanded in the fp32 unit's named function and in the mixed and half templates (see memc_fi.hpp on why not a forwarding
+// call); halves are read through widen_f32, so that the compiler sees fp32 operands as in the fp32 function.
+#define MEMC_FI_BLEND_BWD_SITE_BODY(T, FT, IM, GT)                                                                          \
     {                                                                                                                 \
         const FiSite s = fi_locate(x, y, W, H, widen_f32<FT>(flow_p[0]), widen_f32<FT>(flow_p[s2c]));                 \
         if (!s.valid) return;                                                                                         \
-        const float g0 = gout_p[0], g1 = gout_p[s1c], gc2 = gout_p[2 * s1c], oc = widen_f32<T>(occ_p[0]);             \
+        const float g0 = widen_f32<GT>(gout_p[0]), g1 = widen_f32<GT>(gout_p[s1c]),                                   \
+                    gc2 = widen_f32<GT>(gout_p[2 * s1c]), oc = widen_f32<T>(occ_p[0]);                                \
         float gx = 0.0f, gy = 0.0f, gc = 0.0f;                                                                        \
         for (int k = 0; k < 4; k++) {                                                                                 \
-            const float *row = in_b + (int64_t)clampi(s.iy - 1 + k, H - 1) * s1h;                                     \
+            const st_t<IM> *row = in_b + (int64_t)clampi(s.iy - 1 + k, H - 1) * s1h;                                  \
             for (int m = 0; m < 4; m++) {                                                                             \
-                const float *p = row + clampi(s.ix - 1 + m, W - 1);                                                   \
+                const st_t<IM> *p = row + clampi(s.ix - 1 + m, W - 1);                                                \
                 float sv = 0.0f;                                                                                      \
-                sv += g0 * p[0];  sv += g1 * p[s1c];  sv += gc2 * p[2 * s1c];                                         \
+                sv += g0 * widen_f32<IM>(p[0]);  sv += g1 * widen_f32<IM>(p[s1c]);  sv += gc2 * widen_f32<IM>(p[2 * s1c]); \
                 const float wa = m < 2 ? (1 - s.a) : s.a, wb = k < 2 ? (1 - s.b) : s.b;                               \
                 const float gt = (wa * wb) * sv, tap = widen_f32<T>(tap_p[(k * 4 + m) * s3c]);                        \
                 g3[(k * 4 + m) * s3c] = narrow_f32<T>(oc * gt);                                                       \
@@ -109,32 +112,50 @@ __device__ __noinline__ inline void fi_blend_bwd_site(int x, int y, int W, int H
                                                       const float *flow_p, float *g2, int64_t s2c, const float *tap_p,
                                                       float *g3, int64_t s3c, const float *gout_p, const float *occ_p,
                                                       float *gocc_p)
-MEMC_FI_BLEND_BWD_SITE_BODY(F32, F32)
+MEMC_FI_BLEND_BWD_SITE_BODY(F32, F32, F32, F32)
 template <class T, class FT>
 __device__ __noinline__ void fi_blend_bwd_site_mx(int x, int y, int W, int H, const float *in_b, int64_t s1c, int s1h,
                                                   const st_t<FT> *flow_p, st_t<FT> *g2, int64_t s2c, const st_t<T> *tap_p,
                                                   st_t<T> *g3, int64_t s3c, const float *gout_p, const st_t<T> *occ_p,
                                                   st_t<T> *gocc_p)
-MEMC_FI_BLEND_BWD_SITE_BODY(T, FT)
+MEMC_FI_BLEND_BWD_SITE_BODY(T, FT, F32, F32)
+// the same with the image stored as the taps are and a gradoutput of storage GT (libmemc_hip_lp_blend_grad.so)
+template <class T, class FT, class GT>
+__device__ __noinline__ void fi_blend_bwd_site_lp(int x, int y, int W, int H, const st_t<T> *in_b, int64_t s1c, int s1h,
+                                                  const st_t<FT> *flow_p, st_t<FT> *g2, int64_t s2c, const st_t<T> *tap_p,
+                                                  st_t<T> *g3, int64_t s3c, const st_t<GT> *gout_p, const st_t<T> *occ_p,
+                                                  st_t<T> *gocc_p)
+MEMC_FI_BLEND_BWD_SITE_BODY(T, FT, T, GT)
 #undef MEMC_FI_BLEND_BWD_SITE_BODY
 
 // A quad that contains an invalid site first stores its 16 + 2 + 1 quads: zeros to the tap and flow gradients
 // (fi_bwd_zero_invalid), and to the occlusion gradient, per site, 0 where the site is valid and sum_c gout_c * in_c(x, y)
 // where it is not -- the forward copies the input pixel at a site whose target lies outside the image, so that is what
 // the occlusion multiplies there (summed in fp32, narrowed once).  The quad's valid sites are then stored site by site by
-// the same lane, and therefore after these.
-template <class T = F32, class FT = F32>
-__device__ __forceinline__ void fi_blend_bwd_store_invalid(bool inb, unsigned valid, const f32x4 (&go)[3], const float *in_b,
-                                                           int64_t s1c, unsigned o1, st_t<FT> *gflow_b, int64_t s2c,
+// the same lane, and therefore after these.  (oi: the byte offset of the quad in the image's planes, of storage IM.)
+template <class T = F32, class FT = F32, class IM = F32>
+__device__ __forceinline__ void fi_blend_bwd_store_invalid(bool inb, unsigned valid, const f32x4 (&go)[3],
+                                                           const st_t<IM> *in_b, int64_t s1c, unsigned oi,
+                                                           st_t<FT> *gflow_b, int64_t s2c,
                                                            unsigned o2, st_t<T> *gfilt_b, int64_t s3c, unsigned o3,
                                                            st_t<T> *gocc_b, unsigned o4)
 {
     fi_bwd_zero_invalid<T, FT>(inb, valid, gflow_b, s2c, o2, gfilt_b, s3c, o3);
     if (!inb || valid == 0xFu) return;         // rare (image borders, |flow| guard): ordinary 64-bit addressing
-    const float *p = in_b + o1 / 4u;
     f32x4 gc = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (sizeof(st_t<IM>) == 4) {
+        const float *p = in_b + oi / 4u;
 #pragma unroll
-    for (int c = 0; c < 3; c++) gc += go[c] * *reinterpret_cast<const f32x4u *>(p + c * s1c);
+        for (int c = 0; c < 3; c++) gc += go[c] * *reinterpret_cast<const f32x4u *>(p + c * s1c);
+    } else {
+        const st_t<IM> *p = in_b + oi / 2u;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            f32x4 px = widen4<IM>(*reinterpret_cast<const u16x4a *>(p + c * s1c));
+            asm volatile("" : "+v"(px));       // an fp32 operand, as in the fp32 kernel (widen_f32 of memc_lp.hpp)
+            gc += go[c] * px;
+        }
+    }
 #pragma unroll
     for (int j = 0; j < 4; j++) gc[j] = ((valid >> j) & 1u) ? 0.0f : gc[j];
     if constexpr (sizeof(st_t<T>) == 4) {

@@ -32,6 +32,8 @@ __global__ __launch_bounds__(256, 2) void fi_blend_bwd_c3_mx(
     const st_t<T> *__restrict__ occ, const float *__restrict__ gout, st_t<FT> *__restrict__ gflow,
     st_t<T> *__restrict__ gfilt, st_t<T> *__restrict__ gocc)
 {
+    using I = F32;                             // the image and gradoutput are fp32
+    using GT = F32;
     constexpr int NT = 256;
 #include "fi_blend_bwd_c3_body.inc"
 }

@@ -1,5 +1,5 @@
 """What the ctypes bindings of the satellite warp libraries share (my_lib_lp, my_lib_lp_grad, my_lib_blend_grad, my_lib_mx,
-my_lib_mx_grad, my_lib_mx_blend_grad): the tensor descriptor, the dtype codes and one loader.  Importing this loads nothing."""
+my_lib_mx_grad, my_lib_mx_blend_grad, my_lib_lp_blend_grad): the tensor descriptor, the dtype codes and one loader.  Importing this loads nothing."""
 import ctypes
 import os
 import threading

@@ -22,6 +22,16 @@ per-direction backward launches run on the half kernel of libmemc_hip_lp_grad.so
 of two widened halves).  Elsewhere they run the float32 kernel on the widened inputs.  Each gradient comes back in its
 input's dtype.
 
+`FilterInterpolationBlendLayer(fused_half_backward=True)` (off by default: the routes above are what a layer constructed
+without it takes, bit for bit) changes the backward of such a pure half call per direction: a direction whose image needs
+no gradient is ONE kernel of libmemc_hip_lp_blend_grad.so (include/memc_warp_lp_blend_grad.h) on the saved half tensors and
+the gradoutput as it arrives -- the float32 fused kernel's arithmetic on the exactly widened values, each gradient rounded
+once to its input's dtype, nothing widened or narrowed on the host (about 96 B per site moved; the composed route moves
+several hundred), image gradient None.  Its flow, tap and occlusion gradients are those of the float32 layer's fused route
+on the widened tensors, cast once.  A direction whose image does need a gradient, or that the library declines (a view that
+is not made of 8-byte quads, another shape), takes the composed route above, unchanged.  float32 and mixed calls ignore
+the switch.
+
 Mixed precision (what torch.autocast hands over: float32 frames, float16 / bfloat16 taps and occlusions of one dtype): RGB,
 the 4x4 filter and a width that is a multiple of four from 8 on run ONE kernel of libmemc_hip_mx.so on the tensors as they
 are -- the half kernel's float32 arithmetic, the float32 result unrounded -- instead of widening taps, occlusions and flows
@@ -40,6 +50,7 @@ from torch.autograd.function import once_differentiable
 import my_package._ext.my_lib as my_lib
 import my_package._ext.my_lib_blend_grad as my_lib_blend_grad
 import my_package._ext.my_lib_lp as my_lib_lp
+import my_package._ext.my_lib_lp_blend_grad as my_lib_lp_blend_grad
 import my_package._ext.my_lib_mx as my_lib_mx
 from ._common import cast, check, f32c, flow_dtype, payload_dtype, require_gpu
 from .FilterInterpolationLayer import FilterInterpolationLayer, backward_lp, lp_backward_covered, mx_covered
@@ -167,6 +178,43 @@ class _FilterInterpolationBlendLpFunction(Function):
         return tuple(g.to(t.dtype) for g, t in zip(grads, saved))
 
 
+def _direction_backward_fused_lp(x, flow, filt, occ, gradoutput):
+    """(flow, tap, occlusion) gradients of ONE pure half direction of the blend whose image wants no gradient, from ONE
+    kernel of libmemc_hip_lp_blend_grad.so on the tensors as they are (every element of the three is assigned), each in its
+    input's dtype.  None where the library declines the call (nothing touched)."""
+    g_flow, g_filt, g_occ = torch.empty_like(flow), torch.empty_like(filt), torch.empty_like(occ)
+    status = my_lib_lp_blend_grad.FilterInterpolationBlendLayer_gpu_backward_lp(x, flow, filt, occ, gradoutput, g_flow,
+                                                                                g_filt, g_occ)
+    if status == 1:
+        return None
+    check(status, "FilterInterpolationBlendLayer_gpu_backward_lp")
+    return g_flow, g_filt, g_occ
+
+
+class _FilterInterpolationBlendLpFusedFunction(_FilterInterpolationBlendLpFunction):
+    """float16 / bfloat16 with fused_half_backward: the forward of _FilterInterpolationBlendLpFunction; backward per
+    direction: an image that wants no gradient on libmemc_hip_lp_blend_grad.so, on the saved tensors and the gradoutput as
+    they are; any other direction, and one the library declines, the composed route of _FilterInterpolationBlendLpFunction"""
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gradoutput):
+        saved, gradoutput = ctx.saved_tensors, gradoutput.contiguous()
+        grads, wide = [], None
+        for d in (0, 1):
+            direction, fused = saved[d::2], None             # (x, flow, filt, occ), contiguous already
+            if not ctx.needs_input_grad[d]:
+                fused = _direction_backward_fused_lp(*direction, gradoutput)   # in the inputs' dtypes
+            if fused is not None:
+                grads.append((None,) + fused)
+            else:                                            # the image gradient is wanted, or declined: composed
+                if wide is None:
+                    wide = gradoutput.float().contiguous()
+                g = _direction_grads(tuple(t.float().contiguous() for t in direction), wide, saved[d:6:2], True)
+                grads.append(tuple(gi.to(t.dtype) for gi, t in zip(g, direction)))
+        return _interleave(grads)
+
+
 def _blend_forward_fp32(args):
     """the blend of eight contiguous float32 tensors: the fused kernel where it takes the call, else two warps"""
     if fused_supported(args[0], args[4], args[1], args[2], args[3], args[5], args[6], args[7]):
@@ -221,7 +269,12 @@ def blend_mx_covered(input0, input2, flow0, flow1, filter0, filter1, occlusion0,
 
 
 class FilterInterpolationBlendLayer(object):
-    """`FilterInterpolationBlendLayer()(input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1)`"""
+    """`FilterInterpolationBlendLayer()(input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1)`;
+    fused_half_backward: the backward of a pure float16 / bfloat16 call takes libmemc_hip_lp_blend_grad.so for every
+    direction whose image needs no gradient (see the module's docstring)"""
+
+    def __init__(self, fused_half_backward=False):
+        self.fused_half_backward = fused_half_backward
 
     def __call__(self, input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):
         require_gpu("FilterInterpolationBlendLayer", input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1)
@@ -232,7 +285,9 @@ class FilterInterpolationBlendLayer(object):
         dtype = payload_dtype(input0, input2, filter0, filter1, occlusion0, occlusion1)
         if dtype != torch.float32:
             fdt = flow_dtype(flow0, dtype) if flow_dtype(flow0, dtype) == flow_dtype(flow1, dtype) else torch.float32
-            return _FilterInterpolationBlendLpFunction.apply(
+            function = _FilterInterpolationBlendLpFusedFunction if self.fused_half_backward \
+                else _FilterInterpolationBlendLpFunction
+            return function.apply(
                 cast(input0, dtype), cast(input2, dtype), cast(flow0, fdt), cast(flow1, fdt), cast(filter0, dtype),
                 cast(filter1, dtype), cast(occlusion0, dtype), cast(occlusion1, dtype))
         input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1 = (

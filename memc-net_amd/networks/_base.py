@@ -48,6 +48,11 @@ class MEMCNetBase(nn.Module):
         # plus two context warps (2705 vs 2485 us at 8x720x1280, 64 context channels: the context kernel sits at 239
         # of 256 VGPRs and the extra image chunk makes the compiler's chunk loop ~15 % slower), so off by default
         self.fused_context = False
+        # a cast (pure float16 / bfloat16) model: the blend's backward as one kernel per direction on the half tensors as
+        # they are (libmemc_hip_lp_blend_grad.so) instead of widening, two float32 recomputations and the warp's whole
+        # backward; float32 and autocast calls ignore it.  Off by default: the composed route is the one the networks'
+        # recorded calls pin (profiles/r18_half_blend_backward.txt has the measured ratio)
+        self.fused_half_blend_backward = False
         fs2 = filter_size * filter_size
         self.initScaleNets_filter = unet_trunk(2 * channel, align_corners, batch_norm)
         self.initScaleNets_filter1 = unet_head(fs2)
@@ -146,8 +151,8 @@ class MEMCNetBase(nn.Module):
             extra = (ctx0, ctx2)
         else:
             if self.fused_blend and FilterInterpolationBlendModule is not None:
-                blended = FilterInterpolationBlendModule()(frame0, frame2, flows[0], flows[1], filters[0], filters[1],
-                                                           occlusions[0], occlusions[1])
+                blended = FilterInterpolationBlendModule(self.fused_half_blend_backward)(
+                    frame0, frame2, flows[0], flows[1], filters[0], filters[1], occlusions[0], occlusions[1])
             else:
                 blended = (occlusions[0] * warp(frame0, flows[0], filters[0])
                            + occlusions[1] * warp(frame2, flows[1], filters[1]))

@@ -22,7 +22,15 @@ The `mixed_blend` group (--only mixed_blend) is ONE direction of the blend layer
 that are data: the promoted route (the direction's saved flow, taps and occlusion cast to float32, the float32 fused kernel
 of libmemc_hip_blend_grad.so, the three gradients cast back: what _FilterInterpolationBlendMxFunction.backward ran before
 libmemc_hip_mx_blend_grad.so and still runs where that library declines) against the one kernel on the tensors as they
-are (_direction_backward_fused)."""
+are (_direction_backward_fused).
+
+The `half_blend` group (--only half_blend) is ONE direction of the blend layer's backward for a PURE half call (a model cast
+to bfloat16 / float16) with frames that are data: the composed route, which stays the layer's default (the direction's four
+saved tensors and the gradoutput widened, a float32 forward recomputation, two elementwise passes and a channel sum, a
+zero-filled image gradient, the warp's whole backward on libmemc_hip_lp_grad.so, four narrowing casts: what
+_FilterInterpolationBlendLpFunction.backward runs per direction) against the one kernel of libmemc_hip_lp_blend_grad.so on
+the tensors as they are (_direction_backward_fused_lp: what FilterInterpolationBlendLayer(fused_half_backward=True) runs).
+In these rows `widened` is the composed route and `native` the one kernel."""
 import argparse
 import json
 import math
@@ -48,13 +56,13 @@ def _sets(shape, n, blend, T, half_flow, seed, mixed=False):
     ft = T if half_flow else torch.float32
     out = []
     it = torch.float32 if mixed else T                        # the image and gradoutput of a mixed call stay float32
-    if blend == "one":                                        # one direction of the mixed blend
+    if blend == "one":                                        # one direction of the mixed (or the pure half) blend
         for i in range(n):
             t = synth.torch_inputs("cuda", B, C, H, W, flow_kind="smooth", seed=seed + 97 * i)
             g = torch.Generator("cuda").manual_seed(seed + i)
-            out.append({"x": t["x"], "flow": t["flow"].to(ft), "filt": t["filt"].to(T),
+            out.append({"x": t["x"].to(it), "flow": t["flow"].to(ft), "filt": t["filt"].to(T),
                         "occ": torch.rand(B, 1, H, W, device="cuda", generator=g).to(T),
-                        "gout": torch.randn(B, C, H, W, device="cuda", generator=g)})
+                        "gout": torch.randn(B, C, H, W, device="cuda", generator=g).to(it)})
         return out
     for i in range(n):
         t = synth.torch_inputs("cuda", B, C, H, W, flow_kind="smooth", seed=seed + 97 * i)
@@ -118,6 +126,19 @@ def _callers(op, sets, want1):
             grads = BL._direction_backward_fused(s["x"], s["flow"], s["filt"], s["occ"], s["gout"])
             assert grads is not None, "not covered"
             return grads
+    elif op == "lpblend":
+        def widened():                                       # the composed route of one direction: the layer's default
+            s = pick()
+            saved = (s["x"], s["flow"], s["filt"], s["occ"])
+            grads = BL._direction_grads(tuple(t.float().contiguous() for t in saved), s["gout"].float().contiguous(),
+                                        saved[:3], True)
+            return tuple(g.to(t.dtype) for g, t in zip(grads, saved))
+
+        def native():
+            s = pick()
+            grads = BL._direction_backward_fused_lp(s["x"], s["flow"], s["filt"], s["occ"], s["gout"])
+            assert grads is not None, "not covered"
+            return grads
     else:
         def _blend(half):
             s = pick()
@@ -141,8 +162,11 @@ def run_case(name, op, shape, T, half_flow, want1, rounds, iters):
         per_set = B * H * W * (2 * C * 4 + 16 * 2 + 2 * 4)    # float32 image and gradoutput, half taps
     if op == "mxblend":
         per_set = B * H * W * (2 * C * 4 + 16 * 2 + 2 * 4 + 2)
+    if op == "lpblend":
+        per_set = B * H * W * (2 * C * 2 + 16 * 2 + 2 * 4 + 2)
     n = max(2, math.ceil(ROTATE_BYTES / per_set))
-    sets = _sets(shape, n, "one" if op == "mxblend" else op == "blend", T, half_flow, seed=2468, mixed=op == "mx")
+    sets = _sets(shape, n, "one" if op in ("mxblend", "lpblend") else op == "blend", T, half_flow, seed=2468,
+                 mixed=op in ("mx", "mxblend"))
     calls = _callers(op, sets, want1)
     times = {"widened": [], "native": []}
     for _ in range(rounds):
@@ -196,6 +220,14 @@ def main():
                 cases.append(("mixed_blend_bwd %s %s %s flow" % (tname, "x".join(map(str, shape)),
                                                                  "T" if half_flow else "fp32"),
                               "mxblend", shape, T, half_flow, False))
+    # the pure half blend group: one direction, frames that are data; the composed route (the default) against
+    # libmemc_hip_lp_blend_grad.so
+    for shape in (big, (8, 3, 256, 448)):
+        for tname, T in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
+            for half_flow in (False, True):
+                cases.append(("half_blend_bwd %s %s %s flow" % (tname, "x".join(map(str, shape)),
+                                                                "T" if half_flow else "fp32"),
+                              "lpblend", shape, T, half_flow, False))
     rows = []
     for name, op, shape, T, half_flow, want1 in cases:
         if a.only and a.only not in name:

@@ -36,14 +36,14 @@ def make_vars(tree):
     text = open(os.path.join(tree, CSRC, "Makefile")).read()
     find = lambda name: re.search(r"^%s\s*[?:]?=\s*(.*)$" % name, text, re.M)
     get = lambda name: find(name).group(1).split() if find(name) else []       # (a list an older Makefile lacks: empty)
-    return {n: get(n) for n in ("ARCH", "CXXFLAGS", "SRCS", "ARMS", "SRCS_LP", "SRCS_LPG", "SRCS_BG", "SRCS_MX", "SRCS_MXG", "SRCS_MXBG")}
+    return {n: get(n) for n in ("ARCH", "CXXFLAGS", "SRCS", "ARMS", "SRCS_LP", "SRCS_LPG", "SRCS_BG", "SRCS_MX", "SRCS_MXG", "SRCS_MXBG", "SRCS_LPBG")}
 
 
 def units(tree):
     """(label, source, defines): what the libraries are built from, host-only files left out"""
     v = make_vars(tree)
     hip = [s for s in v["SRCS"] if s.endswith(".hip")]
-    return ([("product/" + s, s, []) for s in hip + v["SRCS_LP"] + v["SRCS_LPG"] + v["SRCS_BG"] + v["SRCS_MX"] + v["SRCS_MXG"] + v["SRCS_MXBG"]] +
+    return ([("product/" + s, s, []) for s in hip + v["SRCS_LP"] + v["SRCS_LPG"] + v["SRCS_BG"] + v["SRCS_MX"] + v["SRCS_MXG"] + v["SRCS_MXBG"] + v["SRCS_LPBG"]] +
             [("measure/" + s, s, ["-DMEMC_MEASURE"]) for s in hip + v["ARMS"]])
 
 
