@@ -46,16 +46,6 @@ __global__ __launch_bounds__(NT, 2) void fi_blend_bwd_c3(
 #include "fi_blend_bwd_c3_body.inc"
 }
 
-// The tiles cover the width's quads: 64 x NT / 16 sites each.
-template <int NT = 256>
-static void launch_fi_blend_bwd_c3(const FiBlendBwdCall<> &k)
-{
-    const TileGrid g = fi_tile_grid<TileGeom<16, 3072, NT>>(k.w, k.h);
-    hipLaunchKernelGGL((fi_blend_bwd_c3<NT>), dim3((unsigned)g.ntx * g.nty * k.batch), dim3(NT), PkGeomT<NT>::kLds, k.stream,
-                       k.w, k.h, g.ntx, g.nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h,
-                       k.s4.b, k.s4.h, k.in1, k.flow, k.filt, k.occ, k.gout, k.gflow, k.gfilt, k.gocc);
-}
-
 }  // namespace memc
 
 // ==================================================================================================
@@ -74,29 +64,20 @@ int FilterInterpolationBlendLayer_gpu_backward(memc_stream_t stream, const memc_
                                                const memc_tensor4 *gradoutput, const memc_tensor4 *gradflow,
                                                const memc_tensor4 *gradfilter, const memc_tensor4 *gradocclusion)
 {
-    for (const memc_tensor4 *t : {input, flow, filter, occlusion, gradoutput, gradflow, gradfilter, gradocclusion})
-        if (!ok(t)) return kErr;
-    if (!flow_matches(input, flow) || !taps_match(input, filter) || !occlusion_matches(input, occlusion)) return kErr;
-    const int fs = fi_filter_side_exact(filter->size[1]);
-    if (fs < 1) return kErr;
-    if (!same_layout(input, gradoutput) || !same_layout(flow, gradflow) || !same_layout(filter, gradfilter) ||
-        !same_layout(occlusion, gradocclusion))
-        return kErr;
-    const FiChecked q = fi_sizes(fs, input);
+    const FiChecked q = fi_blend_bwd_checked(fi_filter_side_exact, input, flow, filter, occlusion, gradoutput, gradflow,
+                                             gradfilter, gradocclusion);
     if (q.done) return q.code;
     // coverage: the tiled RGB kernel; anything else is the caller's composition of the warp's entry points
-    if (!(fi_rgb_tiled_shape(q.c, fs, q.w) &&
+    if (!(fi_rgb_tiled_shape(q.c, q.fs, q.w) &&
           plane_fits_u32(q.w, q.h, {(long)input->stride[2], (long)flow->stride[2], (long)filter->stride[2],
                                     (long)occlusion->stride[2]})))
         return kNotCovered;
-    const FiBlendBwdCall<> k = {
-        (hipStream_t)stream, q.w, q.h, q.n, plane(input), plane(flow), plane(filter), plane(occlusion),
-        reinterpret_cast<const float *>(input->data), reinterpret_cast<const float *>(flow->data),
-        reinterpret_cast<const float *>(filter->data), reinterpret_cast<const float *>(occlusion->data),
-        reinterpret_cast<const float *>(gradoutput->data), reinterpret_cast<float *>(gradflow->data),
-        reinterpret_cast<float *>(gradfilter->data), reinterpret_cast<float *>(gradocclusion->data)};
+    constexpr int NT = 256;                    // one 64 x NT / 16 tile of sites per workgroup
     t_blend_grad_path = "fi_blend_bwd:tiled_c3";
-    launch_fi_blend_bwd_c3<256>(k);
+    fi_blend_bwd_tiled_launch<TileGeom<16, 3072, NT>>(
+        fi_blend_bwd_c3<NT>, PkGeomT<NT>::kLds,
+        fi_blend_bwd_call<F32, F32, F32>((hipStream_t)stream, q, input, flow, filter, occlusion, gradoutput, gradflow,
+                                         gradfilter, gradocclusion));
     return launch_status();
 }
 

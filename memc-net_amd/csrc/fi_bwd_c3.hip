@@ -11,7 +11,9 @@
 //   * sites whose window no band covers are redone by fi_bwd_site_scalar with global atomics.
 // The packed planes are described in memc_pk.hpp.  The kernel of rounds 1-2 (one fp64 plane per colour) lives on as a
 // measurement arm: arms/fi_bwd_c3_arms.hip.  The kernel's body and its per-site helpers live in memc_fi_bwd_c3.hpp, written
-// over the tensors' storage: this file instantiates them for fp32, lp_fi_bwd_c3.hip for fp16 / bf16.
+// over the tensors' storage: this file instantiates them for fp32, lp_fi_bwd_c3.hip for fp16 / bf16, mx_fi_bwd_c3.hip for an
+// fp32 image beside half taps (those two launch through memc_fi_abi.hpp's fi_bwd_tiled_launch; launch_fi_bwd_c3_pk below
+// covers the whole quads of a ragged width, w & ~3, and serves the measurement arms, so it keeps its own grid).
 #include "memc_common.hpp"
 #include "memc_internal.h"
 #include "memc_fi_bwd_c3.hpp"

@@ -42,20 +42,7 @@ __global__ __launch_bounds__(256, 2) void fi_blend_bwd_c3_lp(
 // ==================================================================================================
 // C ABI (include/memc_warp_lp_blend_grad.h)
 // ==================================================================================================
-namespace {
-
 using namespace memc;
-
-template <class T, class FT, class GT>
-void launch_fi_blend_bwd_c3_lp(const FiBlendBwdCall<st_t<T>, st_t<FT>, st_t<T>, st_t<GT>> &k)
-{
-    const TileGrid g = fi_tile_grid<TileGeom<16>>(k.w, k.h);
-    hipLaunchKernelGGL((fi_blend_bwd_c3_lp<T, FT, GT>), dim3((unsigned)g.ntx * g.nty * k.batch), dim3(256), PkGeom::kLds,
-                       k.stream, k.w, k.h, g.ntx, g.nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b,
-                       k.s3.c, k.s3.h, k.s4.b, k.s4.h, k.in1, k.flow, k.filt, k.occ, k.gout, k.gflow, k.gfilt, k.gocc);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -70,37 +57,26 @@ int FilterInterpolationBlendLayer_gpu_backward_lp(memc_stream_t stream, memc_dty
                                                   const memc_tensor4 *gradfilter, const memc_tensor4 *gradocclusion)
 {
     if (!dtypes_ok(payload, flowt) || !dtypes_ok(payload, goutt)) return kErr;
-    for (const memc_tensor4 *t : {input, flow, filter, occlusion, gradoutput, gradflow, gradfilter, gradocclusion})
-        if (!ok(t)) return kErr;
-    if (!flow_matches(input, flow) || !taps_match(input, filter) || !occlusion_matches(input, occlusion)) return kErr;
-    const int fs = fi_filter_side_exact(filter->size[1]);
-    if (fs < 1) return kErr;
-    if (!same_layout(input, gradoutput) || !same_layout(flow, gradflow) || !same_layout(filter, gradfilter) ||
-        !same_layout(occlusion, gradocclusion))
-        return kErr;
-    const FiChecked q = fi_sizes(fs, input);
+    const FiChecked q = fi_blend_bwd_checked(fi_filter_side_exact, input, flow, filter, occlusion, gradoutput, gradflow,
+                                             gradfilter, gradocclusion);
     if (q.done) return q.code;
-    // coverage: the tiled RGB kernel on 8-byte half quads; anything else is the caller's (composed) business
-    bool covered = fi_rgb_tiled_shape(q.c, fs, q.w) &&
-                   plane_fits_u32(q.w, q.h, {(long)input->stride[2], (long)flow->stride[2], (long)filter->stride[2],
-                                             (long)occlusion->stride[2]});
-    for (const memc_tensor4 *t : {input, filter, occlusion, gradfilter, gradocclusion}) covered = covered && quad_ok(t);
-    if (flowt == payload) covered = covered && quad_ok(flow) && quad_ok(gradflow);
-    else covered = covered && dword_ok(flow) && dword_ok(gradflow);
-    if (goutt == payload) covered = covered && quad_ok(gradoutput);
-    else covered = covered && dword_ok(gradoutput);
-    if (!covered) return kNotCovered;
+    // coverage: the tiled RGB kernel, every tensor aligned for its storage; anything else is the caller's (composed) business
+    if (!(fi_rgb_tiled_shape(q.c, q.fs, q.w) &&
+          plane_fits_u32(q.w, q.h, {(long)input->stride[2], (long)flow->stride[2], (long)filter->stride[2],
+                                    (long)occlusion->stride[2]}) &&
+          storage_ok(payload, {input, filter, occlusion, gradfilter, gradocclusion}) &&
+          storage_ok(flowt, {flow, gradflow}) && storage_ok(goutt, {gradoutput})))
+        return kNotCovered;
     // the eight (payload, flow, gradoutput) instantiations
     return fi_dispatch(payload, flowt, goutt, [&](auto t, auto ft, auto gt) {
         using T = decltype(t);
         using FT = decltype(ft);
         using GT = decltype(gt);
-        const FiBlendBwdCall<st_t<T>, st_t<FT>, st_t<T>, st_t<GT>> k = {
-            (hipStream_t)stream, q.w, q.h, q.n, plane(input), plane(flow), plane(filter), plane(occlusion),
-            data_of<T>(input), data_of<FT>(flow), data_of<T>(filter), data_of<T>(occlusion), data_of<GT>(gradoutput),
-            data_of<FT>(gradflow), data_of<T>(gradfilter), data_of<T>(gradocclusion)};
         t_lp_blend_grad_path = "fi_blend_bwd_lp:tiled_c3";
-        launch_fi_blend_bwd_c3_lp<T, FT, GT>(k);
+        fi_blend_bwd_tiled_launch<TileGeom<16>>(
+            fi_blend_bwd_c3_lp<T, FT, GT>, PkGeom::kLds,
+            fi_blend_bwd_call<T, FT, GT>((hipStream_t)stream, q, input, flow, filter, occlusion, gradoutput, gradflow,
+                                         gradfilter, gradocclusion));
         return launch_status();
     });
 }

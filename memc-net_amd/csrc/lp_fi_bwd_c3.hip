@@ -40,20 +40,7 @@ __global__ __launch_bounds__(256, 2) void fi_bwd_c3_lp(
 // ==================================================================================================
 // C ABI (include/memc_warp_lp_grad.h)
 // ==================================================================================================
-namespace {
-
 using namespace memc;
-
-template <class P, class FT, class GT, int PART>
-void launch_fi_bwd_c3_lp(const FiBwdCall<st_t<P>, st_t<FT>, st_t<GT>> &k)
-{
-    const TileGrid g = fi_tile_grid<TileGeom<16>>(k.w, k.h);
-    hipLaunchKernelGGL((fi_bwd_c3_lp<P, FT, GT, PART>), dim3((unsigned)g.ntx * g.nty * k.batch), dim3(256), PkGeom::kLds,
-                       k.stream, k.w, k.h, g.ntx, g.nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b,
-                       k.s3.c, k.s3.h, k.in1, k.flow, k.filt, k.gout, k.gin1, k.gin2, k.gin3);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -86,7 +73,10 @@ int FilterInterpolationLayer_gpu_backward_lp(memc_stream_t stream, memc_dtype pa
         return fi_bwd_launch(fi_bwd_call<P, FT, GT>((hipStream_t)stream, q, input1, input2, input3, gradoutput, gradinput1,
                                                     gradinput2, gradinput3),
                              t_lp_grad_path, "fi_bwd_lp:tiled_c3", "fi_bwd_lp:tiled_c3_noimage",
-                             [](const auto &k, auto part) { launch_fi_bwd_c3_lp<P, FT, GT, decltype(part)::value>(k); });
+                             [](const auto &k, auto part) {
+                                 fi_bwd_tiled_launch<TileGeom<16>>(fi_bwd_c3_lp<P, FT, GT, decltype(part)::value>,
+                                                                   PkGeom::kLds, k);
+                             });
     });
 }
 

@@ -1,8 +1,7 @@
 // memc_desc.hpp -- the descriptor checks of the C ABIs (host code only): layer_api.cpp (include/memc_warp.h) and, through
-// memc_fi_abi.hpp (the check sequences and predicates that only the satellite libraries share), lp_filter_interpolation.hip
-// (memc_warp_lp.h), lp_fi_bwd_c3.hip (memc_warp_lp_grad.h), fi_blend_bwd_c3.hip (memc_warp_blend_grad.h),
-// mx_filter_interpolation.hip (memc_warp_mx.h) and mx_fi_bwd_c3.hip (memc_warp_mx_grad.h).  One contract: every check the
-// reference performs (my_lib_cuda.c, cited where an entry point calls these) and, beyond it, what the kernels rely on --
+// memc_fi_abi.hpp (the check sequences and predicates that only the satellite libraries share), the seven warp libraries
+// among the nine satellites, listed there (the frame I/O and the SSIM library check their own planes).  One contract: every
+// check the reference performs (my_lib_cuda.c, cited where an entry point calls these) and, beyond it, what the kernels rely on --
 // unit w strides, sizes and strides that fit the launchers' `int`, and the b/c/h strides of a tensor that a kernel
 // indexes with ANOTHER tensor's strides (output / gradoutput / gradinput1 with input1's, gradinput2 with input2's,
 // gradinput3 with input3's, exactly as my_lib_kernel.cu does).  The reference leaves those cases unchecked and silently

@@ -1,6 +1,7 @@
 // memc_fi.hpp -- the per-site device helpers of every FilterInterpolation kernel, forward and backward, fp32 and half
 // storage (filter_interpolation.hip, fi_bwd_c3.hip, fi_bwd_cn.hip, fi_blend_bwd_c3.hip, lp_filter_interpolation.hip,
-// lp_fi_bwd_c3.hip, mx_filter_interpolation.hip, mx_fi_bwd_c3.hip, arms/; their host side: memc_fi_abi.hpp):
+// lp_fi_bwd_c3.hip, lp_fi_blend_bwd_c3.hip, mx_filter_interpolation.hip, mx_fi_bwd_c3.hip, mx_fi_blend_bwd_c3.hip, arms/;
+// the satellites' host side: memc_fi_abi.hpp):
 // the geometry of a lane's four sites, the LDS gather, the one-site paths from global memory.
 //
 // What the fp32 kernels and their half twins share is written ONCE here, as a macro wherever a shared always-inline

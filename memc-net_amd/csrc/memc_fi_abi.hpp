@@ -2,17 +2,19 @@
 // (memc_warp_lp.h), lp_fi_bwd_c3.hip (memc_warp_lp_grad.h), fi_blend_bwd_c3.hip (memc_warp_blend_grad.h),
 // mx_filter_interpolation.hip (memc_warp_mx.h), mx_fi_bwd_c3.hip (memc_warp_mx_grad.h), mx_fi_blend_bwd_c3.hip
 // (memc_warp_mx_blend_grad.h) and lp_fi_blend_bwd_c3.hip (memc_warp_lp_blend_grad.h).  The filter-side rules, the
-// coverage predicates, the two check sequences that more than one entry point runs, the tile grid, the call descriptors
-// filled from the tensors, the backward's PART choice and the dtype dispatch.  An entry point keeps its dtype check, its
-// filter-side rule, its coverage test and its path strings; the order of every sequence is memc_desc.hpp's contract:
-// malformed (-1), then empty (0), then -- the entry point's own -- not covered (1), then the launch.
+// coverage predicates, the three check sequences that more than one entry point runs, the tile grid, the call descriptors
+// filled from the tensors, the launch of the tiled backward kernels, the backward's PART choice and the dtype dispatch.  An
+// entry point keeps its dtype check, its filter-side rule, its coverage test and its path strings; the order of every
+// sequence is memc_desc.hpp's contract: malformed (-1), then empty (0), then -- the entry point's own -- not covered (1),
+// then the launch.
 #pragma once
 
 #include "memc_common.hpp"                     // launch_status
 #include "memc_desc.hpp"
 #include "memc_launch.hpp"
-#include "memc_lp.hpp"                         // the storage tags F32 / F16 / BF16
+#include "memc_lp.hpp"                         // the storage tags F32 / F16 / BF16; memc_tile.hpp: TileGeom
 
+#include <initializer_list>
 #include <math.h>
 #include <type_traits>
 
@@ -36,8 +38,15 @@ inline bool occlusion_matches(const memc_tensor4 *in1, const memc_tensor4 *occ)
     return occ->size[0] == in1->size[0] && occ->size[1] == 1 && occ->size[2] == in1->size[2] && occ->size[3] == in1->size[3];
 }
 
-// fp32 tensors of the mixed libraries need dword alignment only (f32x4u); a half tensor 8-byte quads (quad_ok)
+// Aligned for its storage: an fp32 tensor needs dword alignment only (f32x4u), a half tensor 8-byte quads (quad_ok).
+// `ts`: tensors stored as `dt`; a NULL one (an optional gradient) passes.
 inline bool dword_ok(const memc_tensor4 *t) { return reinterpret_cast<uintptr_t>(t->data) % 4 == 0; }
+inline bool storage_ok(memc_dtype dt, std::initializer_list<const memc_tensor4 *> ts)
+{
+    for (const memc_tensor4 *t : ts)
+        if (t && !(dt == MEMC_F32 ? dword_ok(t) : quad_ok(t))) return false;
+    return true;
+}
 
 // the shapes the RGB tiled kernels take: whole quads, at least two of them
 inline bool fi_rgb_tiled_shape(int c, int fs, int w) { return c == 3 && fs == 4 && w % 4 == 0 && w >= 8; }
@@ -69,6 +78,24 @@ inline FiChecked fi_bwd_checked(int (*side)(int64_t), const memc_tensor4 *input1
         !same_layout(input3, gradinput3) || !same_layout(input1, gradoutput))
         return bad;                                                                 // :719-723
     return fi_sizes(fs, input1);
+}
+
+// One direction of the blend's backward: its eight tensors (no image gradient).
+inline FiChecked fi_blend_bwd_checked(int (*side)(int64_t), const memc_tensor4 *input, const memc_tensor4 *flow,
+                                      const memc_tensor4 *filter, const memc_tensor4 *occlusion,
+                                      const memc_tensor4 *gradoutput, const memc_tensor4 *gradflow,
+                                      const memc_tensor4 *gradfilter, const memc_tensor4 *gradocclusion)
+{
+    const FiChecked bad = {true, kErr, 0, 0, 0, 0, 0};
+    for (const memc_tensor4 *t : {input, flow, filter, occlusion, gradoutput, gradflow, gradfilter, gradocclusion})
+        if (!ok(t)) return bad;
+    if (!flow_matches(input, flow) || !taps_match(input, filter) || !occlusion_matches(input, occlusion)) return bad;
+    const int fs = side(filter->size[1]);
+    if (fs < 1) return bad;
+    if (!same_layout(input, gradoutput) || !same_layout(flow, gradflow) || !same_layout(filter, gradfilter) ||
+        !same_layout(occlusion, gradocclusion))
+        return bad;
+    return fi_sizes(fs, input);
 }
 
 // The blend forward's nine tensors: input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1, output.
@@ -127,6 +154,36 @@ inline FiBwdCall<st_t<T>, st_t<FT>, st_t<GT>, st_t<IT>> fi_bwd_call(
     return {stream, q.w, q.h, q.c, q.n, q.fs, plane(in1), plane(flow), plane(filt),
             data_of<IT>(in1), data_of<FT>(flow), data_of<T>(filt), data_of<GT>(gout),
             data_of<F32>(gin1), data_of<FT>(gin2), data_of<T>(gin3)};
+}
+
+template <class T, class FT, class GT, class IT = T>
+inline FiBlendBwdCall<st_t<T>, st_t<FT>, st_t<IT>, st_t<GT>> fi_blend_bwd_call(
+    hipStream_t stream, const FiChecked &q, const memc_tensor4 *in1, const memc_tensor4 *flow, const memc_tensor4 *filt,
+    const memc_tensor4 *occ, const memc_tensor4 *gout, const memc_tensor4 *gflow, const memc_tensor4 *gfilt,
+    const memc_tensor4 *gocc)
+{
+    return {stream, q.w, q.h, q.n, plane(in1), plane(flow), plane(filt), plane(occ),
+            data_of<IT>(in1), data_of<FT>(flow), data_of<T>(filt), data_of<T>(occ), data_of<GT>(gout),
+            data_of<FT>(gflow), data_of<T>(gfilt), data_of<T>(gocc)};
+}
+
+// The launch of a tiled RGB backward kernel: one workgroup of G::kThreads lanes and `lds` bytes per tile of geometry G,
+// one argument list per family -- the warp's seven tensors, the blend direction's eight.
+template <class G, class Kernel, class T, class FT, class GT, class IT>
+inline void fi_bwd_tiled_launch(Kernel kernel, int lds, const FiBwdCall<T, FT, GT, IT> &k)
+{
+    const TileGrid g = fi_tile_grid<G>(k.w, k.h);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)g.ntx * g.nty * k.batch), dim3(G::kThreads), lds, k.stream, k.w, k.h, g.ntx,
+                       g.nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.in1, k.flow,
+                       k.filt, k.gout, k.gin1, k.gin2, k.gin3);
+}
+template <class G, class Kernel, class T, class FT, class IT, class GT>
+inline void fi_blend_bwd_tiled_launch(Kernel kernel, int lds, const FiBlendBwdCall<T, FT, IT, GT> &k)
+{
+    const TileGrid g = fi_tile_grid<G>(k.w, k.h);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)g.ntx * g.nty * k.batch), dim3(G::kThreads), lds, k.stream, k.w, k.h, g.ntx,
+                       g.nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b, k.s3.c, k.s3.h, k.s4.b, k.s4.h,
+                       k.in1, k.flow, k.filt, k.occ, k.gout, k.gflow, k.gfilt, k.gocc);
 }
 
 // The RGB backward's launch: the whole backward where the image gradient is wanted (the fp32 launcher's PART 0), else

@@ -14,24 +14,8 @@
 
 #include "memc_common.hpp"
 #include "memc_fi_bwd_c3.hpp"
-#include "memc_launch.hpp"                     // Plane
 
 namespace memc {
-
-// One direction of the blend's backward.  s1: the image and gradoutput; s2: the flow and its gradient; s3: the taps and
-// their gradient; s4: the occlusion and its gradient (one channel: no channel stride).  T / FT / IT / GT: element types.
-template <class T = float, class FT = float, class IT = float, class GT = float>
-struct FiBlendBwdCall {
-    hipStream_t stream;
-    int w, h, batch;
-    Plane s1, s2, s3, s4;
-    const IT *in1;
-    const FT *flow;
-    const T *filt, *occ;
-    const GT *gout;
-    FT *gflow;
-    T *gfilt, *gocc;
-};
 
 // fi_bwd_phase1 (memc_fi_bwd_c3.hpp) for the blend: quads whose four sites the band covers.  Same loop order and the same
 // laundering -- read the comments there before rearranging anything: the nest lives on staying clear of spills.

@@ -5,7 +5,7 @@
 // launch_fi_bwd_image_owner in fi_bwd_cn.hip, ...).  The measurement build's arms are one function per entry point, in
 // arms/ (fi_fwd_arm_launch, proj_fwd_arm_launch, ...).  The warps' descriptors are templates over the
 // tensors' storage: float in the fp32 library, st_t<...> (memc_lp.hpp) in the half-precision and mixed ones, which fill
-// them from the memc_tensor4s with memc_fi_abi.hpp's fi_fwd_call / fi_blend_fwd_call / fi_bwd_call.
+// them from the memc_tensor4s with memc_fi_abi.hpp's fi_fwd_call / fi_blend_fwd_call / fi_bwd_call / fi_blend_bwd_call.
 #pragma once
 
 #include "memc_warp_lp.h"                      // memc_tensor4
@@ -54,6 +54,17 @@ struct FiBwdCall {
     Plane s1, s2, s3;
     const IT *in1;  const FT *flow;  const T *filt;  const GT *gout;
     float *gin1;  FT *gin2;  T *gin3;
+};
+
+// One direction of the blend's backward (no image gradient).  s1: the image and gradoutput; s2: the flow and its gradient;
+// s3: the taps and their gradient; s4: the occlusion and its gradient (one channel: s4.c is not used).
+template <class T = float, class FT = float, class IT = float, class GT = float>
+struct FiBlendBwdCall {
+    hipStream_t stream;
+    int w, h, batch;
+    Plane s1, s2, s3, s4;
+    const IT *in1;  const FT *flow;  const T *filt, *occ;  const GT *gout;
+    FT *gflow;  T *gfilt, *gocc;
 };
 
 // The bilinear warp (Interpolation / InterpolationCh).  s1: input1, output / gradoutput, gradinput1; s2: the flow, gradinput2.

@@ -43,20 +43,7 @@ __global__ __launch_bounds__(256, 2) void fi_blend_bwd_c3_mx(
 // ==================================================================================================
 // C ABI (include/memc_warp_mx_blend_grad.h)
 // ==================================================================================================
-namespace {
-
 using namespace memc;
-
-template <class T, class FT>
-void launch_fi_blend_bwd_c3_mx(const FiBlendBwdCall<st_t<T>, st_t<FT>> &k)
-{
-    const TileGrid g = fi_tile_grid<TileGeom<16>>(k.w, k.h);
-    hipLaunchKernelGGL((fi_blend_bwd_c3_mx<T, FT>), dim3((unsigned)g.ntx * g.nty * k.batch), dim3(256), PkGeom::kLds,
-                       k.stream, k.w, k.h, g.ntx, g.nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b,
-                       k.s3.c, k.s3.h, k.s4.b, k.s4.h, k.in1, k.flow, k.filt, k.occ, k.gout, k.gflow, k.gfilt, k.gocc);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -71,34 +58,24 @@ int FilterInterpolationBlendLayer_gpu_backward_mx(memc_stream_t stream, memc_dty
                                                   const memc_tensor4 *gradfilter, const memc_tensor4 *gradocclusion)
 {
     if (!dtypes_ok(tapt, flowt)) return kErr;
-    for (const memc_tensor4 *t : {input, flow, filter, occlusion, gradoutput, gradflow, gradfilter, gradocclusion})
-        if (!ok(t)) return kErr;
-    if (!flow_matches(input, flow) || !taps_match(input, filter) || !occlusion_matches(input, occlusion)) return kErr;
-    const int fs = fi_filter_side_exact(filter->size[1]);
-    if (fs < 1) return kErr;
-    if (!same_layout(input, gradoutput) || !same_layout(flow, gradflow) || !same_layout(filter, gradfilter) ||
-        !same_layout(occlusion, gradocclusion))
-        return kErr;
-    const FiChecked q = fi_sizes(fs, input);
+    const FiChecked q = fi_blend_bwd_checked(fi_filter_side_exact, input, flow, filter, occlusion, gradoutput, gradflow,
+                                             gradfilter, gradocclusion);
     if (q.done) return q.code;
-    // coverage: the tiled RGB kernel on 8-byte half quads; anything else is the caller's (promoted) business
-    bool covered = fi_rgb_tiled_shape(q.c, fs, q.w) &&
-                   plane_fits_u32(q.w, q.h, {(long)input->stride[2], (long)flow->stride[2], (long)filter->stride[2],
-                                             (long)occlusion->stride[2]});
-    for (const memc_tensor4 *t : {filter, occlusion, gradfilter, gradocclusion}) covered = covered && quad_ok(t);
-    for (const memc_tensor4 *t : {input, gradoutput}) covered = covered && dword_ok(t);
-    if (flowt == tapt) covered = covered && quad_ok(flow) && quad_ok(gradflow);
-    else covered = covered && dword_ok(flow) && dword_ok(gradflow);
-    if (!covered) return kNotCovered;
+    // coverage: the tiled RGB kernel, every tensor aligned for its storage; anything else is the caller's (promoted) business
+    if (!(fi_rgb_tiled_shape(q.c, q.fs, q.w) &&
+          plane_fits_u32(q.w, q.h, {(long)input->stride[2], (long)flow->stride[2], (long)filter->stride[2],
+                                    (long)occlusion->stride[2]}) &&
+          storage_ok(tapt, {filter, occlusion, gradfilter, gradocclusion}) && storage_ok(MEMC_F32, {input, gradoutput}) &&
+          storage_ok(flowt, {flow, gradflow})))
+        return kNotCovered;
     return fi_dispatch(tapt, flowt, [&](auto t, auto ft) {
         using T = decltype(t);
         using FT = decltype(ft);
-        const FiBlendBwdCall<st_t<T>, st_t<FT>> k = {
-            (hipStream_t)stream, q.w, q.h, q.n, plane(input), plane(flow), plane(filter), plane(occlusion),
-            data_of<F32>(input), data_of<FT>(flow), data_of<T>(filter), data_of<T>(occlusion), data_of<F32>(gradoutput),
-            data_of<FT>(gradflow), data_of<T>(gradfilter), data_of<T>(gradocclusion)};
         t_mx_blend_grad_path = "fi_blend_bwd_mx:tiled_c3";
-        launch_fi_blend_bwd_c3_mx<T, FT>(k);
+        fi_blend_bwd_tiled_launch<TileGeom<16>>(
+            fi_blend_bwd_c3_mx<T, FT>, PkGeom::kLds,
+            fi_blend_bwd_call<T, FT, F32, F32>((hipStream_t)stream, q, input, flow, filter, occlusion, gradoutput, gradflow,
+                                               gradfilter, gradocclusion));
         return launch_status();
     });
 }

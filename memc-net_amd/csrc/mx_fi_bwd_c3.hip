@@ -45,20 +45,7 @@ __global__ __launch_bounds__(256, 2) void fi_bwd_c3_mx(
 // ==================================================================================================
 // C ABI (include/memc_warp_mx_grad.h)
 // ==================================================================================================
-namespace {
-
 using namespace memc;
-
-template <class T, class FT, int PART>
-void launch_fi_bwd_c3_mx(const FiBwdCall<st_t<T>, st_t<FT>, float, float> &k)
-{
-    const TileGrid g = fi_tile_grid<TileGeom<16>>(k.w, k.h);
-    hipLaunchKernelGGL((fi_bwd_c3_mx<T, FT, PART>), dim3((unsigned)g.ntx * g.nty * k.batch), dim3(256), PkGeom::kLds,
-                       k.stream, k.w, k.h, g.ntx, g.nty, k.batch, k.s1.b, k.s1.c, k.s1.h, k.s2.b, k.s2.c, k.s2.h, k.s3.b,
-                       k.s3.c, k.s3.h, k.in1, k.flow, k.filt, k.gout, k.gin1, k.gin2, k.gin3);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -76,22 +63,22 @@ int FilterInterpolationLayer_gpu_backward_mx(memc_stream_t stream, memc_dtype ta
     const FiChecked q = fi_bwd_checked(fi_filter_side_exact, input1, input2, input3, gradoutput, gradinput1, gradinput2,
                                        gradinput3);
     if (q.done) return q.code;
-    // coverage: the tiled RGB kernel on 8-byte half quads; anything else is the caller's (promoted) business
-    bool covered = fi_rgb_tiled_shape(q.c, q.fs, q.w) &&
-                   plane_fits_u32(q.w, q.h, {(long)input1->stride[2], (long)input2->stride[2], (long)input3->stride[2]});
-    for (const memc_tensor4 *t : {input3, gradinput3}) covered = covered && quad_ok(t);
-    for (const memc_tensor4 *t : {input1, gradoutput}) covered = covered && dword_ok(t);
-    if (gradinput1) covered = covered && dword_ok(gradinput1);
-    if (flowt == tapt) covered = covered && quad_ok(input2) && quad_ok(gradinput2);
-    else covered = covered && dword_ok(input2) && dword_ok(gradinput2);
-    if (!covered) return kNotCovered;
+    // coverage: the tiled RGB kernel, every tensor aligned for its storage; anything else is the caller's (promoted) business
+    if (!(fi_rgb_tiled_shape(q.c, q.fs, q.w) &&
+          plane_fits_u32(q.w, q.h, {(long)input1->stride[2], (long)input2->stride[2], (long)input3->stride[2]}) &&
+          storage_ok(tapt, {input3, gradinput3}) && storage_ok(MEMC_F32, {input1, gradoutput, gradinput1}) &&
+          storage_ok(flowt, {input2, gradinput2})))
+        return kNotCovered;
     return fi_dispatch(tapt, flowt, [&](auto t, auto ft) {
         using T = decltype(t);
         using FT = decltype(ft);
         return fi_bwd_launch(fi_bwd_call<T, FT, F32, F32>((hipStream_t)stream, q, input1, input2, input3, gradoutput,
                                                           gradinput1, gradinput2, gradinput3),
                              t_mx_grad_path, "fi_bwd_mx:tiled_c3", "fi_bwd_mx:tiled_c3_noimage",
-                             [](const auto &k, auto part) { launch_fi_bwd_c3_mx<T, FT, decltype(part)::value>(k); });
+                             [](const auto &k, auto part) {
+                                 fi_bwd_tiled_launch<TileGeom<16>>(fi_bwd_c3_mx<T, FT, decltype(part)::value>,
+                                                                   PkGeom::kLds, k);
+                             });
     });
 }
 

@@ -4,44 +4,37 @@
         + occlusion1 * FilterInterpolation(input2, flow1, filter1)
 
 i.e. `FilterInterpolate` of networks/MEMC_Net_star.py:264-277 as ONE kernel (the two warped frames are never
-written).  Differentiable; nothing but the inputs is kept for the backward pass.  float32: a direction whose image
-does not need a gradient (the frames of the networks are data) is ONE kernel of libmemc_hip_blend_grad.so
-(include/memc_warp_blend_grad.h) on the raw gradoutput: flow, tap and occlusion gradients in one pass, image gradient None.
-A direction whose image does need one, or a shape that kernel does not cover, is composed from the reference-API entry
-points (a forward recomputation + a backward launch), as every direction was before that kernel existed.
+written).  Differentiable; nothing but the inputs is kept for the backward pass.  Every kernel does float32 arithmetic on
+the exactly widened values and rounds each stored value once; each gradient comes back in its input's dtype.
 
-The fused kernel covers what the networks use (RGB, 4x4 filters, widths a multiple of 4); any other shape is
-composed from FilterInterpolationLayer calls -- same values, no error.
+The routes, by the dtypes of the call ("half": float16 or bfloat16; "tiled": RGB, 4x4 filters, a width that is a multiple
+of four from 8 on).  The backward is taken per direction d.  "composed" is _direction_backward: the warp's forward
+recomputed, two elementwise passes, a zero-filled image gradient and the warp's whole backward, in float32.  "fused" is
+ONE kernel on the raw gradoutput for a direction whose image needs no gradient (the frames of the networks are data):
+flow, tap and occlusion gradients in one pass, image gradient None.  A library declines with return code 1 and has
+touched nothing then.
 
-float16 / bfloat16 (functions/_common.py: payload_dtype): the payload dtype is torch.promote_types over the images, the
-taps and the occlusions, which are cast to it; the flows stay float32 or that dtype.  The forward is one kernel of
-libmemc_hip_lp.so for every shape (fp32 arithmetic, one rounding of the blended value).  The backward of a half call
-recomputes both warps and the occlusion gradients in float32 on the widened inputs, as the float32 path does; its two
-per-direction backward launches run on the half kernel of libmemc_hip_lp_grad.so wherever it covers the direction (RGB,
-16 taps, width a multiple of four), on the half image and taps, with the float32 gradoutput * occlusion (exact: a product
-of two widened halves).  Elsewhere they run the float32 kernel on the widened inputs.  Each gradient comes back in its
-input's dtype.
+  call                        forward                   backward of direction d                             where the library declines
+  --------------------------  ------------------------  --------------------------------------------------  --------------------------
+  float32, fused_supported    libmemc_hip, one kernel   no image gradient: fused, libmemc_hip_blend_grad    composed
+                                                        (176 B per site); else composed, libmemc_hip
+  float32, any other shape    two FilterInterpolationLayer calls and the blend in torch: same values, autograd's backward
+  float32 images, half taps   libmemc_hip_mx on the     no image gradient: fused, on the saved tensors as   forward: widened, the
+  and occlusions, tiled       tensors as they are       they are, libmemc_hip_mx_blend_grad (108 B per      float32 rows; backward:
+  (blend_mx_covered: what     (112 B per site;          site; promoted: about 380); else the saved tensors  as "else"
+  torch.autocast makes)       promoted: 416)            widened, the float32 rows, gradients cast back
+  half payload                libmemc_hip_lp, any       composed on the widened tensors; where tiled, the   the warp's backward on
+                              shape                     warp's backward on libmemc_hip_lp_grad (half image  libmemc_hip, widened
+                                                        and taps, the float32 gradoutput * occlusion)
+  half payload and            as above                  no image gradient: fused, on the saved tensors and  the row above
+  fused_half_backward=True                              the gradoutput as it arrives (96 B per site),
+                                                        libmemc_hip_lp_blend_grad; else the row above
+  any other mix               cast to the payload dtype (functions/_common.py: payload_dtype over images, taps and
+                              occlusions; the flows stay float32 or that dtype): the float32 or the half rows
 
-`FilterInterpolationBlendLayer(fused_half_backward=True)` (off by default: the routes above are what a layer constructed
-without it takes, bit for bit) changes the backward of such a pure half call per direction: a direction whose image needs
-no gradient is ONE kernel of libmemc_hip_lp_blend_grad.so (include/memc_warp_lp_blend_grad.h) on the saved half tensors and
-the gradoutput as it arrives -- the float32 fused kernel's arithmetic on the exactly widened values, each gradient rounded
-once to its input's dtype, nothing widened or narrowed on the host (about 96 B per site moved; the composed route moves
-several hundred), image gradient None.  Its flow, tap and occlusion gradients are those of the float32 layer's fused route
-on the widened tensors, cast once.  A direction whose image does need a gradient, or that the library declines (a view that
-is not made of 8-byte quads, another shape), takes the composed route above, unchanged.  float32 and mixed calls ignore
-the switch.
-
-Mixed precision (what torch.autocast hands over: float32 frames, float16 / bfloat16 taps and occlusions of one dtype): RGB,
-the 4x4 filter and a width that is a multiple of four from 8 on run ONE kernel of libmemc_hip_mx.so on the tensors as they
-are -- the half kernel's float32 arithmetic, the float32 result unrounded -- instead of widening taps, occlusions and flows
-on the host first (112 B per site moved instead of 416).  Where that library declines (a view it cannot read) the call is
-promoted to float32 as before.  The backward of a direction whose image needs no gradient is ONE kernel of
-libmemc_hip_mx_blend_grad.so (include/memc_warp_mx_blend_grad.h) on the saved tensors as they are and the float32
-gradoutput: the float32 fused kernel's arithmetic, each gradient rounded once to its input's dtype (108 B per site moved
-instead of about 380).  A direction whose image does need one, or that the library declines, widens its saved tensors and
-runs the float32 backward above, then casts each gradient back.  Either way the gradients are those of the promoted call,
-bit for bit, each in its input's dtype.  Any other mix of dtypes is promoted by payload_dtype as before.
+The fused mixed gradients are the promoted call's, bit for bit; the fused half ones those of the float32 fused route on the
+widened tensors, cast once.  float32 and mixed calls ignore fused_half_backward; without it a half call never reaches
+libmemc_hip_lp_blend_grad.  Each library in turn, with its timings: INTEGRATION.md.
 """
 import torch
 from torch.autograd import Function
@@ -52,7 +45,7 @@ import my_package._ext.my_lib_blend_grad as my_lib_blend_grad
 import my_package._ext.my_lib_lp as my_lib_lp
 import my_package._ext.my_lib_lp_blend_grad as my_lib_lp_blend_grad
 import my_package._ext.my_lib_mx as my_lib_mx
-from ._common import cast, check, f32c, flow_dtype, payload_dtype, require_gpu
+from ._common import LOWP, cast, cast_like, check, declined, f32c, flow_dtype, payload_dtype, require_gpu
 from .FilterInterpolationLayer import FilterInterpolationLayer, backward_lp, lp_backward_covered, mx_covered
 
 
@@ -98,17 +91,21 @@ def _direction_backward(x, flow, filt, occ, gradoutput, half=None):
 
 def _direction_backward_fused(x, flow, filt, occ, gradoutput):
     """(flow, tap, occlusion) gradients of ONE direction of the blend whose image wants no gradient, from ONE kernel on the
-    raw float32 gradoutput (every element of the three is assigned), each in its input's dtype: libmemc_hip_blend_grad.so
-    for float32 tensors, libmemc_hip_mx_blend_grad.so for a float32 image beside half taps and occlusion.  None where that
-    kernel does not cover the call (anything but RGB, 16 taps and a width that is a multiple of four from 8 on; a half
-    view that is not made of 8-byte quads)."""
+    tensors as they are and the raw gradoutput (every element of the three is assigned), each in its input's dtype:
+    libmemc_hip_lp_blend_grad.so for a half image; else my_lib_blend_grad's door: libmemc_hip_blend_grad.so for float32
+    tensors, libmemc_hip_mx_blend_grad.so for a float32 image beside half taps and occlusion.  None where the library
+    declines the call (anything but RGB, 16 taps and a width that is a multiple of four from 8 on; a half view that is
+    not made of 8-byte quads)."""
     g_flow, g_filt, g_occ = torch.empty_like(flow), torch.empty_like(filt), torch.empty_like(occ)
-    status = my_lib_blend_grad.FilterInterpolationBlendLayer_gpu_backward(x, flow, filt, occ, gradoutput, g_flow, g_filt,
-                                                                          g_occ)
-    if status == 1:
-        return None
-    check(status, "FilterInterpolationBlendLayer_gpu_backward")
-    return g_flow, g_filt, g_occ
+    if x.dtype in LOWP:
+        name = "FilterInterpolationBlendLayer_gpu_backward_lp"
+        err = my_lib_lp_blend_grad.FilterInterpolationBlendLayer_gpu_backward_lp(x, flow, filt, occ, gradoutput, g_flow,
+                                                                                 g_filt, g_occ)
+    else:
+        name = "FilterInterpolationBlendLayer_gpu_backward"
+        err = my_lib_blend_grad.FilterInterpolationBlendLayer_gpu_backward(x, flow, filt, occ, gradoutput, g_flow, g_filt,
+                                                                           g_occ)
+    return None if declined(err, name) else (g_flow, g_filt, g_occ)
 
 
 def _blend_backward(saved, gradoutput, half=None, needs_image_grad=(True, True)):
@@ -175,44 +172,39 @@ class _FilterInterpolationBlendLpFunction(Function):
     def backward(ctx, gradoutput):
         saved = ctx.saved_tensors
         grads = _blend_backward(tuple(t.float().contiguous() for t in saved), gradoutput.float().contiguous(), half=saved)
-        return tuple(g.to(t.dtype) for g, t in zip(grads, saved))
+        return cast_like(grads, saved)
 
 
-def _direction_backward_fused_lp(x, flow, filt, occ, gradoutput):
-    """(flow, tap, occlusion) gradients of ONE pure half direction of the blend whose image wants no gradient, from ONE
-    kernel of libmemc_hip_lp_blend_grad.so on the tensors as they are (every element of the three is assigned), each in its
-    input's dtype.  None where the library declines the call (nothing touched)."""
-    g_flow, g_filt, g_occ = torch.empty_like(flow), torch.empty_like(filt), torch.empty_like(occ)
-    status = my_lib_lp_blend_grad.FilterInterpolationBlendLayer_gpu_backward_lp(x, flow, filt, occ, gradoutput, g_flow,
-                                                                                g_filt, g_occ)
-    if status == 1:
-        return None
-    check(status, "FilterInterpolationBlendLayer_gpu_backward_lp")
-    return g_flow, g_filt, g_occ
+def _backward_on_saved(ctx, gradoutput, half):
+    """The backward of the two Functions that hand the saved tensors to a fused kernel as they are.  Per direction: an
+    image that wants no gradient takes _direction_backward_fused; where it does, or the library declines, the direction is
+    widened, takes _direction_grads and each gradient is cast back.  half: a pure half call -- composed with the half
+    tensors (so that libmemc_hip_lp_grad.so takes the warp's backward), the gradoutput widened once and only if some
+    direction needs it; else a mixed call with a float32 gradoutput -- the float32 routes for the real need."""
+    saved, grads, wide = ctx.saved_tensors, [], None
+    for d in (0, 1):
+        direction, fused = saved[d::2], None                 # (x, flow, filt, occ), contiguous already
+        if not ctx.needs_input_grad[d]:
+            fused = _direction_backward_fused(*direction, gradoutput)          # in the inputs' dtypes
+        if fused is not None:
+            grads.append((None,) + fused)
+            continue
+        if wide is None:
+            wide = gradoutput.float().contiguous()
+        g = _direction_grads(tuple(t.float().contiguous() for t in direction), wide, saved[d:6:2] if half else None,
+                             half or ctx.needs_input_grad[d])
+        grads.append(cast_like(g, direction))
+    return _interleave(grads)
 
 
 class _FilterInterpolationBlendLpFusedFunction(_FilterInterpolationBlendLpFunction):
-    """float16 / bfloat16 with fused_half_backward: the forward of _FilterInterpolationBlendLpFunction; backward per
-    direction: an image that wants no gradient on libmemc_hip_lp_blend_grad.so, on the saved tensors and the gradoutput as
-    they are; any other direction, and one the library declines, the composed route of _FilterInterpolationBlendLpFunction"""
+    """float16 / bfloat16 with fused_half_backward: the forward of _FilterInterpolationBlendLpFunction, the backward on
+    libmemc_hip_lp_blend_grad.so wherever a direction's image wants no gradient (_backward_on_saved)"""
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gradoutput):
-        saved, gradoutput = ctx.saved_tensors, gradoutput.contiguous()
-        grads, wide = [], None
-        for d in (0, 1):
-            direction, fused = saved[d::2], None             # (x, flow, filt, occ), contiguous already
-            if not ctx.needs_input_grad[d]:
-                fused = _direction_backward_fused_lp(*direction, gradoutput)   # in the inputs' dtypes
-            if fused is not None:
-                grads.append((None,) + fused)
-            else:                                            # the image gradient is wanted, or declined: composed
-                if wide is None:
-                    wide = gradoutput.float().contiguous()
-                g = _direction_grads(tuple(t.float().contiguous() for t in direction), wide, saved[d:6:2], True)
-                grads.append(tuple(gi.to(t.dtype) for gi, t in zip(g, direction)))
-        return _interleave(grads)
+        return _backward_on_saved(ctx, gradoutput.contiguous(), half=True)
 
 
 def _blend_forward_fp32(args):
@@ -227,36 +219,23 @@ def _blend_forward_fp32(args):
 
 class _FilterInterpolationBlendMxFunction(Function):
     """float32 images, float16 / bfloat16 taps and occlusions, flows in float32 or that dtype: forward on libmemc_hip_mx.so
-    (where it declines: promoted to float32, the float32 kernels); backward: a direction whose image wants no gradient on
-    libmemc_hip_mx_blend_grad.so, on the tensors as they are; any other direction the promoted call's, on widened tensors"""
+    (where it declines: promoted to float32, the float32 kernels); backward on libmemc_hip_mx_blend_grad.so wherever a
+    direction's image wants no gradient (_backward_on_saved)"""
 
     @staticmethod
     def forward(ctx, input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):
         args = tuple(t.contiguous() for t in (input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1))
         output = torch.empty_like(args[0])                   # every element is written
         err = my_lib_mx.FilterInterpolationBlendLayer_gpu_forward_mx(*args, output)
-        if err == 1:                                         # declined, nothing touched: the promoted route
+        if declined(err, "FilterInterpolationBlendLayer_gpu_forward_mx"):      # the promoted route
             output = _blend_forward_fp32(tuple(t.float() for t in args))
-        else:
-            check(err, "FilterInterpolationBlendLayer_gpu_forward_mx")
         ctx.save_for_backward(*args)
         return output
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gradoutput):
-        saved, gradoutput = ctx.saved_tensors, f32c(gradoutput)
-        grads = []
-        for d in (0, 1):
-            direction, fused = saved[d::2], None             # (x, flow, filt, occ), contiguous already
-            if not ctx.needs_input_grad[d]:
-                fused = _direction_backward_fused(*direction, gradoutput)      # in the inputs' dtypes
-            if fused is not None:
-                grads.append((None,) + fused)
-            else:                                            # declined, or the image gradient is wanted: promoted
-                g = _direction_grads(tuple(t.float() for t in direction), gradoutput, None, ctx.needs_input_grad[d])
-                grads.append(tuple(None if gi is None else gi.to(t.dtype) for gi, t in zip(g, direction)))
-        return _interleave(grads)
+        return _backward_on_saved(ctx, f32c(gradoutput), half=False)
 
 
 def blend_mx_covered(input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1):

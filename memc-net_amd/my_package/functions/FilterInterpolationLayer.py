@@ -11,23 +11,27 @@ Differences, all deliberate:
     here the contiguous copies are what the kernel sees;
   * a non-zero return code raises instead of being ignored (:29) / printed (:56-57);
   * CPU tensors raise (the reference's CPU branch dies with NameError);
-  * float16 / bfloat16 (functions/_common.py: payload_dtype): the payload dtype of a call is torch.promote_types over
-    input1 and input3, which are cast to it; the flow stays float32 or that dtype.  The forward runs on the half kernels
-    of libmemc_hip_lp.so and returns that dtype.  The backward of a half call with three channels, the 4x4 filter and a
-    width that is a multiple of four (from 8 on) runs on the half kernel of libmemc_hip_lp_grad.so: the same arithmetic
-    as the float32 backward on the widened inputs, each flow / tap gradient rounded once, the image gradient an fp32
-    buffer rounded afterwards.  Any other half call widens the saved inputs to float32, runs the float32 backward
-    kernels and returns each gradient in its input's dtype.
-  * mixed precision (what torch.autocast hands over: a float32 image, float16 / bfloat16 taps): three channels, the 4x4
-    filter and a width that is a multiple of four from 8 on run ONE kernel of libmemc_hip_mx.so on the tensors as they are
-    -- the half kernels' float32 arithmetic, the float32 result unrounded -- instead of widening the taps and the flow on
-    the host first (60 B per site moved instead of 204).  Where that library declines (a view it cannot read) the call is
-    promoted to float32 as before.  The backward runs ONE kernel of libmemc_hip_mx_grad.so on the saved tensors as they
-    are (the float32 image, the half taps, the float32 gradient of the float32 output): the float32 backward's arithmetic
-    on the widened inputs, each flow / tap gradient rounded once, the image gradient (only where autograd asks for it)
-    float32 -- bit for bit the flow and tap gradients of the promoted call, without its widening and narrowing passes
-    (104 B per site moved instead of about 360).  Where that library declines, the saved tensors are widened and the
-    float32 backward runs, as before.  Any other mixed call is promoted as before.
+  * float16 / bfloat16 and mixed precision, by the dtypes of the call (functions/_common.py: payload_dtype is
+    torch.promote_types over input1 and input3; "half" is float16 or bfloat16; the flow stays float32 or the half dtype,
+    any other flow dtype is cast to float32; "covered" is three channels, the 4x4 filter, a width that is a multiple of
+    four from 8 on: lp_backward_covered).  A library declines with return code 1 and has touched nothing then.
+
+    image, taps        forward                      backward                                   where the library declines
+    -----------------  ---------------------------  -----------------------------------------  ------------------------------
+    float32, float32   libmemc_hip                  libmemc_hip                                (raises)
+    half, half         libmemc_hip_lp, any shape    covered: libmemc_hip_lp_grad on the saved  widened to float32: libmemc_hip,
+                                                    tensors and the gradoutput as it arrives   each gradient cast back
+                                                    (92 B per site; widened: 168 B and the
+                                                    casts); not covered: as declined
+    float32, half,     libmemc_hip_mx on the        libmemc_hip_mx_grad on the saved tensors   forward: flow and taps widened,
+    covered            tensors as they are (60 B    as they are and the float32 gradoutput     libmemc_hip; backward: widened,
+    (mx_covered)       per site; promoted: 204)     (104 B per site; promoted: about 360)      libmemc_hip, gradients cast back
+    any other mix      cast to the payload dtype: one of the first two rows
+
+    Every half or mixed kernel does the float32 kernel's arithmetic on the exactly widened values and rounds each stored
+    value once; the image gradient is a float32 buffer (NULL where autograd does not ask for it: _gradinput1_buffer),
+    cast to the image's dtype afterwards.  The mixed routes' flow and tap gradients are those of the promoted call, bit
+    for bit.  Each library in turn, with its timings: INTEGRATION.md.
 """
 import torch
 from torch.autograd import Function
@@ -38,7 +42,7 @@ import my_package._ext.my_lib_lp as my_lib_lp
 import my_package._ext.my_lib_lp_grad as my_lib_lp_grad
 import my_package._ext.my_lib_mx as my_lib_mx
 import my_package._ext.my_lib_mx_grad as my_lib_mx_grad
-from ._common import LOWP, cast, check, f32c, flow_dtype, payload_dtype, require_gpu
+from ._common import LOWP, cast, cast_like, check, declined, f32c, flow_dtype, payload_dtype, require_gpu
 
 
 class _FilterInterpolationFunction(Function):
@@ -62,22 +66,23 @@ class _FilterInterpolationFunction(Function):
         return _backward_fp32(input1, input2, input3, f32c(gradoutput), ctx.needs_input_grad[0])
 
 
+def _gradinput1_buffer(input1, input3, want1):
+    """The float32 gradinput1 a backward entry point is handed.  None (a NULL pointer) where autograd does not ask for it
+    and the libraries serve one -- three channels, the 4x4 filter and a width that is a multiple of four (include/memc_warp.h;
+    the warped frames are data in the reference's networks, MEMC_Net_star.py:266-277): the RGB kernel then skips its
+    accumulation and this layer its zero fill.  Decided up front, so no first call fails; any other call that wants none
+    gets a buffer that is thrown away.  The buffer is the accumulation target, zero-filled (reference :46) -- except where
+    the library STORES gradinput1 on every path (four and more channels with the 4x4 filter; include/memc_warp.h:
+    memc_gradinput1_is_stored): the memset would be a fifth of the call's traffic."""
+    if not want1 and input1.size(1) == 3 and input3.size(1) == 16 and input1.size(3) % 4 == 0:
+        return None
+    stored = my_lib.gradinput1_is_stored(int(input3.size(1) ** 0.5 + 1e-6), input1.size(1))     # fs as my_lib.c:925
+    return (torch.empty_like if stored else torch.zeros_like)(input1, dtype=torch.float32)
+
+
 def _backward_fp32(input1, input2, input3, gradoutput, want1):
     """(gradinput1 or None, gradinput2, gradinput3) of float32 tensors through the reference-API entry point"""
-    # accumulation target: zero-filled (reference :46) -- except where the library says it STORES gradinput1 on
-    # every path (four and more channels with the 4x4 filter; include/memc_warp.h: memc_gradinput1_is_stored):
-    # the memset would be a fifth of the call's traffic
-    stored = my_lib.gradinput1_is_stored(int(input3.size(1) ** 0.5 + 1e-6), input1.size(1))     # fs as my_lib.c:925
-    # the warped frames are data in the reference's networks (MEMC_Net_star.py:266-277): when autograd does not ask
-    # for gradinput1, the RGB kernel skips its accumulation and this layer its zero fill (a NULL gradinput1,
-    # include/memc_warp.h)
-    # (decided up front -- the library serves a NULL gradinput1 for three channels, the 4x4 filter and a width that is a
-    # multiple of four, include/memc_warp.h; anything else gets a buffer that is thrown away: no failed first call)
-    null_ok = input1.size(1) == 3 and input3.size(1) == 16 and input1.size(3) % 4 == 0
-    if want1 or not null_ok:
-        gradinput1 = torch.empty_like(input1) if stored else torch.zeros_like(input1)
-    else:
-        gradinput1 = None
+    gradinput1 = _gradinput1_buffer(input1, input3, want1)
     # the reference zero-fills these two as well (:47-48); the backward kernels DEFINE every element of them
     # (invalid sites store zero; tests/test_gpu_parity.py::test_backward_defines_flow_and_tap_gradients), so
     # 72 B/site of memsets -- a seventh of the call at 720p -- are skipped
@@ -94,6 +99,13 @@ def _backward_fp32(input1, input2, input3, gradoutput, want1):
     return (gradinput1 if want1 else None), gradinput2, gradinput3
 
 
+def _backward_widened(saved, gradoutput, want1):
+    """the fallback of the half and the mixed Function: the float32 backward on the saved tensors and the gradoutput
+    widened (a float32 one passes as it is), each gradient cast back to its input's dtype"""
+    input1, input2, input3 = (t.float().contiguous() for t in saved)
+    return cast_like(_backward_fp32(input1, input2, input3, gradoutput.float().contiguous(), want1), saved)
+
+
 def lp_backward_covered(input1, input3):
     """What libmemc_hip_lp_grad.so's kernel takes (include/memc_warp_lp_grad.h): three channels, 16 taps, a width that is a
     multiple of four from 8 on.  (Views it declines all the same -- misaligned, say -- come back as return code 1.)"""
@@ -107,21 +119,15 @@ def backward_lp(input1, input2, input3, gradoutput, gradinput1):
     gradinput3 = torch.empty_like(input3)
     err = my_lib_lp_grad.FilterInterpolationLayer_gpu_backward_lp(
         input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3)
-    if err == 1:
+    if declined(err, "FilterInterpolationLayer_gpu_backward_lp"):
         return None
-    check(err, "FilterInterpolationLayer_gpu_backward_lp")
     return gradinput2, gradinput3
 
 
 def _backward_lp(input1, input2, input3, gradoutput, want1):
     """_backward_fp32 on half tensors: the same gradinput1 decision (so the kernel takes the float32 library's PART for the
     call), gradinput1 float32; None where the library does not cover the call"""
-    null_ok = input1.size(1) == 3 and input3.size(1) == 16 and input1.size(3) % 4 == 0
-    if want1 or not null_ok:
-        stored = my_lib.gradinput1_is_stored(int(input3.size(1) ** 0.5 + 1e-6), input1.size(1))
-        gradinput1 = (torch.empty_like if stored else torch.zeros_like)(input1, dtype=torch.float32)
-    else:
-        gradinput1 = None
+    gradinput1 = _gradinput1_buffer(input1, input3, want1)
     if gradoutput.dtype not in (input1.dtype, torch.float32):
         gradoutput = gradoutput.float()
     grads = backward_lp(input1, input2, input3, gradoutput.contiguous(), gradinput1)
@@ -150,10 +156,9 @@ class _FilterInterpolationLpFunction(Function):
         grads = None
         if lp_backward_covered(saved[0], saved[2]):
             grads = _backward_lp(*saved, gradoutput, ctx.needs_input_grad[0])
-        if grads is None:                                    # widened: the float32 kernels
-            input1, input2, input3 = (t.float().contiguous() for t in saved)
-            grads = _backward_fp32(input1, input2, input3, gradoutput.float().contiguous(), ctx.needs_input_grad[0])
-        return tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, saved))
+        if grads is None:
+            return _backward_widened(saved, gradoutput, ctx.needs_input_grad[0])
+        return cast_like(grads, saved)
 
 
 def mx_covered(image, taps):
@@ -171,9 +176,8 @@ def _backward_mx(input1, input2, input3, gradoutput, want1):
     gradinput3 = torch.empty_like(input3)
     err = my_lib_mx_grad.FilterInterpolationLayer_gpu_backward_mx(
         input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3)
-    if err == 1:
+    if declined(err, "FilterInterpolationLayer_gpu_backward_mx"):
         return None
-    check(err, "FilterInterpolationLayer_gpu_backward_mx")
     return gradinput1, gradinput2, gradinput3
 
 
@@ -187,25 +191,20 @@ class _FilterInterpolationMxFunction(Function):
         input1, input2, input3 = input1.contiguous(), input2.contiguous(), input3.contiguous()
         output = torch.empty_like(input1)                    # every element is written
         err = my_lib_mx.FilterInterpolationLayer_gpu_forward_mx(input1, input2, input3, output)
-        if err == 1:                                         # declined, nothing touched: the promoted route
+        if declined(err, "FilterInterpolationLayer_gpu_forward_mx"):      # the promoted route
             err = my_lib.FilterInterpolationLayer_gpu_forward(input1, input2.float(), input3.float(), output)
             check(err, "FilterInterpolationLayer_gpu_forward")
-        else:
-            check(err, "FilterInterpolationLayer_gpu_forward_mx")
         ctx.save_for_backward(input1, input2, input3)
         return output
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gradoutput):
-        saved = ctx.saved_tensors
-        gradoutput = f32c(gradoutput)
+        saved, gradoutput = ctx.saved_tensors, f32c(gradoutput)
         grads = _backward_mx(*saved, gradoutput, ctx.needs_input_grad[0])
         if grads is not None:                                # each gradient in its input's dtype already
             return grads
-        input1, input2, input3 = (t.float() for t in saved)  # declined, nothing touched: the promoted route
-        grads = _backward_fp32(input1, input2, input3, gradoutput, ctx.needs_input_grad[0])
-        return tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, saved))
+        return _backward_widened(saved, gradoutput, ctx.needs_input_grad[0])      # the promoted route
 
 
 class FilterInterpolationLayer(object):

@@ -19,6 +19,15 @@ def check(err, name):
         raise RuntimeError("%s returned %d: shape/stride check failed or the launch failed" % (name, err))
 
 
+def declined(err, name):
+    """Return code 1 of a satellite library: the call is not covered and nothing was touched, so the caller takes its
+    other route -- True.  0: False.  Anything else raises (check)."""
+    if err == 1:
+        return True
+    check(err, name)
+    return False
+
+
 def f32c(t):
     """contiguous float32 view/copy (the reference caches `.contiguous()` copies for backward,
     FilterInterpolationLayer.py:14-16, and only ever sees torch.cuda.FloatTensor)."""
@@ -46,6 +55,11 @@ def payload_dtype(*tensors):
 def cast(t, dtype):
     """`t` in `dtype` (through autograd: the gradient comes back in t's own dtype); no copy when it already is."""
     return t if t.dtype == dtype else t.to(dtype)
+
+
+def cast_like(grads, inputs):
+    """each gradient in its input's dtype; a None stays None"""
+    return tuple(None if g is None else cast(g, t.dtype) for g, t in zip(grads, inputs))
 
 
 def flow_dtype(flow, payload):

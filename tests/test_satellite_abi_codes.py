@@ -1,5 +1,5 @@
-"""The return code of every satellite entry point (libmemc_hip_lp / lp_grad / blend_grad / mx / mx_grad) for a fixed list of
-descriptor mutations of one 2x3x8x16 call, against tests/golden/satellite_abi_codes.json.  The order of the checks is
+"""The return code of every entry point of the seven satellite warp libraries (libmemc_hip_lp / lp_grad / blend_grad / mx /
+mx_grad / mx_blend_grad / lp_blend_grad) for a fixed list of descriptor mutations of one 2x3x8x16 call, against tests/golden/satellite_abi_codes.json.  The order of the checks is
 contract: malformed (-1), then empty (0), then not covered (1), then the launch; a call that is both malformed and not
 covered returns -1.  CPU only: nothing is launched -- a case that the fixture marks as enqueued (L: the covered base call,
 and what the half forwards hand to their one-lane-per-site kernels) is counted and not called.
@@ -35,6 +35,8 @@ ENTRIES = {
     "mx.fwd": ("mx", "FilterInterpolationLayer_gpu_forward_mx", 2, "i3 fF tP i3", (3,), ()),
     "mx.blend": ("mx", "FilterInterpolationBlendLayer_gpu_forward_mx", 2, "i3 i3 fF fF tP tP oP oP i3", (8,), ()),
     "mx_grad.bwd": ("mx_grad", "FilterInterpolationLayer_gpu_backward_mx", 2, "i3 fF tP i3 i3 fF tP", (3, 4, 5, 6), (4,)),
+    "mx_blend_grad.bwd": ("mx_blend_grad", "FilterInterpolationBlendLayer_gpu_backward_mx", 2, "i3 fF tP oP i3 fF tP oP", (4, 5, 6, 7), ()),
+    "lp_blend_grad.bwd": ("lp_blend_grad", "FilterInterpolationBlendLayer_gpu_backward_lp", 3, "iP fF tP oP iG fF tP oP", (4, 5, 6, 7), ()),
 }
 COMBOS = {0: [()],
           2: [(F16, F32), (F16, F16), (BF16, F32), (BF16, BF16), (F32, F32), (F16, BF16), (3, F32)],

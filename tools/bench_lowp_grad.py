@@ -29,7 +29,7 @@ to bfloat16 / float16) with frames that are data: the composed route, which stay
 saved tensors and the gradoutput widened, a float32 forward recomputation, two elementwise passes and a channel sum, a
 zero-filled image gradient, the warp's whole backward on libmemc_hip_lp_grad.so, four narrowing casts: what
 _FilterInterpolationBlendLpFunction.backward runs per direction) against the one kernel of libmemc_hip_lp_blend_grad.so on
-the tensors as they are (_direction_backward_fused_lp: what FilterInterpolationBlendLayer(fused_half_backward=True) runs).
+the tensors as they are (_direction_backward_fused: what FilterInterpolationBlendLayer(fused_half_backward=True) runs).
 In these rows `widened` is the composed route and `native` the one kernel."""
 import argparse
 import json
@@ -136,7 +136,7 @@ def _callers(op, sets, want1):
 
         def native():
             s = pick()
-            grads = BL._direction_backward_fused_lp(s["x"], s["flow"], s["filt"], s["occ"], s["gout"])
+            grads = BL._direction_backward_fused(s["x"], s["flow"], s["filt"], s["occ"], s["gout"])
             assert grads is not None, "not covered"
             return grads
     else:

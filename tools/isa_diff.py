@@ -32,18 +32,22 @@ _RES = (("vgpr", r"; NumVgprs: (\d+)"), ("sgpr", r"; TotalNumSgprs: (\d+)"), ("l
 
 
 def make_vars(tree):
-    """ARCH, CXXFLAGS and the source lists, read from the tree's own Makefile"""
+    """ARCH, CXXFLAGS and the source lists, read from the tree's own Makefile: a new satellite library needs no edit here"""
     text = open(os.path.join(tree, CSRC, "Makefile")).read()
     find = lambda name: re.search(r"^%s\s*[?:]?=\s*(.*)$" % name, text, re.M)
     get = lambda name: find(name).group(1).split() if find(name) else []       # (a list an older Makefile lacks: empty)
-    return {n: get(n) for n in ("ARCH", "CXXFLAGS", "SRCS", "ARMS", "SRCS_LP", "SRCS_LPG", "SRCS_BG", "SRCS_MX", "SRCS_MXG", "SRCS_MXBG", "SRCS_LPBG")}
+    v = {n: get(n) for n in ("ARCH", "CXXFLAGS", "SRCS", "ARMS")}
+    # the satellite libraries: SRCS_<NAME> for every NAME of SATELLITES (an older Makefile without that list: every SRCS_*)
+    names = get("SATELLITES") or re.findall(r"^SRCS_(\w+)\s*:?=", text, re.M)
+    v["SATELLITES"] = [s for n in names for s in get("SRCS_" + n)]
+    return v
 
 
 def units(tree):
     """(label, source, defines): what the libraries are built from, host-only files left out"""
     v = make_vars(tree)
     hip = [s for s in v["SRCS"] if s.endswith(".hip")]
-    return ([("product/" + s, s, []) for s in hip + v["SRCS_LP"] + v["SRCS_LPG"] + v["SRCS_BG"] + v["SRCS_MX"] + v["SRCS_MXG"] + v["SRCS_MXBG"] + v["SRCS_LPBG"]] +
+    return ([("product/" + s, s, []) for s in hip + v["SATELLITES"]] +
             [("measure/" + s, s, ["-DMEMC_MEASURE"]) for s in hip + v["ARMS"]])
 
 
