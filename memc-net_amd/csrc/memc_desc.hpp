@@ -1,6 +1,6 @@
 // memc_desc.hpp -- the descriptor checks of the C ABIs (host code only): layer_api.cpp (include/memc_warp.h) and, through
 // memc_fi_abi.hpp (the check sequences and predicates that only the satellite libraries share), the seven warp libraries
-// among the nine satellites, listed there (the frame I/O and the SSIM library check their own planes).  One contract: every
+// among the ten satellites, listed there (the frame I/O libraries and the SSIM library check their own planes).  One contract: every
 // check the reference performs (my_lib_cuda.c, cited where an entry point calls these) and, beyond it, what the kernels rely on --
 // unit w strides, sizes and strides that fit the launchers' `int`, and the b/c/h strides of a tensor that a kernel
 // indexes with ANOTHER tensor's strides (output / gradoutput / gradinput1 with input1's, gradinput2 with input2's,

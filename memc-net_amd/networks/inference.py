@@ -23,13 +23,44 @@ def pad_amounts(height, width):
     return left, right, top, bottom
 
 
-def interpolate_pairs(model, frame0, frame2, which=1):
+HALF_DTYPES = (torch.float16, torch.bfloat16)
+
+
+def check_precision(dtype, autocast):
+    """The demo loops' two precision arguments: dtype is None, torch.float32 (both: float32 planes, as without it) or a half
+    dtype (the planes handed to the model have it; the caller has cast the model); autocast is None or a half dtype (the
+    model call runs inside torch.autocast on float32 planes).  Any other dtype for either: TypeError; a half dtype together
+    with autocast: ValueError.  Returns the half dtype of the planes, or None for float32 planes."""
+    if dtype is not None and dtype != torch.float32 and dtype not in HALF_DTYPES:
+        raise TypeError("dtype: expected None, torch.float32, torch.float16 or torch.bfloat16, got %r" % (dtype,))
+    if autocast is not None and autocast not in HALF_DTYPES:
+        raise TypeError("autocast: expected None, torch.float16 or torch.bfloat16, got %r" % (autocast,))
+    if dtype in HALF_DTYPES and autocast is not None:
+        raise ValueError("dtype=%s (a cast model) and autocast=%s (a float32 model) exclude each other" % (dtype, autocast))
+    return dtype if dtype in HALF_DTYPES else None
+
+
+def run_model(model, x, autocast=None):
+    """model(x) without gradients, inside torch.autocast(dtype=autocast) where that is asked for"""
+    with torch.no_grad():
+        if autocast is None:
+            return model(x)
+        with torch.autocast(x.device.type, dtype=autocast):
+            return model(x)
+
+
+def interpolate_pairs(model, frame0, frame2, which=1, dtype=None, autocast=None):
     """frame0, frame2: [B, 3, H, W] in [0, 1].  Returns the interpolated middle frames [B, 3, H, W]
-    (which = 1: the rectified output, 0: the blended one -- the demos' `save_which`), padding removed."""
+    (which = 1: the rectified output, 0: the blended one -- the demos' `save_which`), padding removed.
+    dtype=torch.float16 / torch.bfloat16: the frames are cast to it and padded in it (for a model cast with model.to(dtype));
+    autocast=torch.float16 / torch.bfloat16: the model runs inside torch.autocast on the frames as they are (check_precision
+    has the rules).  Either way the result is what the model returns, cropped: its dtype is the model's, not widened here."""
+    half = check_precision(dtype, autocast)
     assert frame0.shape == frame2.shape and frame0.dim() == 4
     h, w = frame0.shape[2], frame0.shape[3]
     left, right, top, bottom = pad_amounts(h, w)
+    if half is not None:
+        frame0, frame2 = frame0.to(half), frame2.to(half)
     x = torch.stack([F.pad(f, (left, right, top, bottom), mode="replicate") for f in (frame0, frame2)])
-    with torch.no_grad():
-        frames, _flows, _filters, _occlusions = model(x)
+    frames, _flows, _filters, _occlusions = run_model(model, x, autocast)
     return frames[which][:, :, top:top + h, left:left + w]

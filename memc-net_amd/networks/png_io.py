@@ -136,12 +136,15 @@ def rgb_scores(rec_rgb, gt_rgb):
 
 
 def interpolate_png_tree(model, data_dir, out_dir, device, gt_dir=None, first="frame10.png", second="frame11.png",
-                         middle="frame10i11.png", which=1):
+                         middle="frame10i11.png", which=1, dtype=None, autocast=None):
     """For every scene directory of data_dir: first + second in, the interpolated middle frame out (out_dir/<scene>/),
     scored against gt_dir/<scene>/<middle> where that exists.  Returns [(scene, mean abs error, PSNR)] (None, None
-    without ground truth).  Scenes that are not three-channel are skipped, as the reference skips them."""
+    without ground truth).  Scenes that are not three-channel are skipped, as the reference skips them.
+    dtype / autocast: interpolate_pairs' (a cast model, or torch.autocast around a float32 one), checked before a file is read;
+    a half result is widened to float32 before it is rounded."""
     import torch
-    from .inference import interpolate_pairs
+    from .inference import check_precision, interpolate_pairs
+    check_precision(dtype, autocast)
     results = []
     for scene in sorted(os.listdir(data_dir)):
         a_path, b_path = os.path.join(data_dir, scene, first), os.path.join(data_dir, scene, second)
@@ -155,7 +158,9 @@ def interpolate_png_tree(model, data_dir, out_dir, device, gt_dir=None, first="f
 
         def to_tensor(img):
             return torch.from_numpy(np.transpose(img, (2, 0, 1)).astype(np.float32) / 255.0).unsqueeze(0).to(device)
-        mid = interpolate_pairs(model, to_tensor(a), to_tensor(b), which)
+        mid = interpolate_pairs(model, to_tensor(a), to_tensor(b), which, dtype=dtype, autocast=autocast)
+        if mid.dtype in (torch.float16, torch.bfloat16):
+            mid = mid.float()                              # numpy has no bfloat16; the widening is exact
         rec = np.round(255.0 * mid.clamp(0.0, 1.0)[0].cpu().numpy()).astype(np.uint8)
         rec = np.ascontiguousarray(np.transpose(rec, (1, 2, 0)))
         os.makedirs(os.path.join(out_dir, scene), exist_ok=True)

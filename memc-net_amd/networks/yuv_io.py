@@ -17,6 +17,8 @@ numpy alone -- the reference needs scipy.misc.imresize and skimage.color for it,
 interpolate_yuv_sequence(..., gpu_io=True) runs the same rule on the device (libmemc_hip_video.so, include/memc_video.h):
 only raw I420 bytes cross the bus (with ssim=True the third score comes from libmemc_hip_ssim.so, include/memc_ssim.h).
 Off by default; the numpy path is the definition the kernels are tested against.
+dtype= / autocast= run the network in float16 / bfloat16 (a cast model, or torch.autocast around a float32 one) on either route;
+with gpu_io=True a cast model's input is decoded by libmemc_hip_video_lp.so (include/memc_video_lp.h).  Off by default as well.
 """
 import numpy as np
 
@@ -153,18 +155,23 @@ def scores_from_sums(sum_abs, sum_sq, pixels):
     return float(int(sum_abs)) / pixels, psnr
 
 
-def _interpolate_yuv_sequence_gpu(model, in_path, out_path, h, w, device, first, last, pairs_per_step, which, ssim=False):
+def _interpolate_yuv_sequence_gpu(model, in_path, out_path, h, w, device, first, last, pairs_per_step, which, ssim=False,
+                                  half=None, autocast=None):
     """interpolate_yuv_sequence with the frame I/O on the device (my_package._ext.my_lib_video, include/memc_video.h): per
     step the raw bytes of frames i, i + 2 and i + 1 of every pair go up, two I420 frames per pair and the integer score
     sums come down.  Decode writes straight into the padded network input; frame i is encoded from its decoded RGB bytes
     (what Yuv420Writer does with the reader's frame), the result from the quantised crop of the network's output.
     ssim=True: one memc_ssim_luma_rgb call per step on the result and the real frame, both on the device already; its
-    doubles share the integer sums' buffer and come down with them."""
+    doubles share the integer sums' buffer and come down with them.
+    half (torch.float16 / torch.bfloat16): the network's input is allocated in that dtype and decoded into by
+    my_package._ext.my_lib_video_lp (include/memc_video_lp.h).  The quantiser follows the dtype of what the model returns:
+    float32 (an autocast run, for one) goes to my_lib_video, a half result to my_lib_video_lp."""
     import torch
     import my_package._ext.my_lib_video as V
+    import my_package._ext.my_lib_video_lp as VL            # loads its library on first use: never in a float32 run
     if ssim:
         import my_package._ext.my_lib_ssim as S
-    from .inference import pad_amounts
+    from .inference import pad_amounts, run_model
     if h % 2 or w % 2:
         raise ValueError("4:2:0 needs even dimensions, got %dx%d" % (w, h))
     device = torch.device(device)
@@ -200,14 +207,16 @@ def _interpolate_yuv_sequence_gpu(model, in_path, out_path, h, w, device, first,
             # [frames i | frames i + 2 | frames i + 1], n of each
             raw = np.frombuffer(b"".join(t[j] for j in (1, 2, 3) for t in batch), dtype=np.uint8)
             raw = torch.from_numpy(raw.copy()).to(device).view(3, n, fb)
-            x = torch.empty((2, n, 3, hp, wp), dtype=torch.float32, device=device)
+            x = torch.empty((2, n, 3, hp, wp), dtype=torch.float32 if half is None else half, device=device)
+            D = V if half is None else VL
             rgb_a, rgb_gt, rec = (torch.empty((n, h, w, 3), dtype=torch.uint8, device=device) for _ in range(3))
-            ok(V.i420_decode(raw[0], n, h, w, rgb=rgb_a, planes=x[0], pads=pads), "memc_i420_decode")
-            ok(V.i420_decode(raw[1], n, h, w, planes=x[1], pads=pads), "memc_i420_decode")
+            ok(D.i420_decode(raw[0], n, h, w, rgb=rgb_a, planes=x[0], pads=pads), "memc_i420_decode")
+            ok(D.i420_decode(raw[1], n, h, w, planes=x[1], pads=pads), "memc_i420_decode")
             ok(V.i420_decode(raw[2], n, h, w, rgb=rgb_gt), "memc_i420_decode")
-            with torch.no_grad():
-                frames, _flows, _filters, _occlusions = model(x)
-            ok(V.rgb_quantise(frames[which][:, :, top:top + h, left:left + w], rec), "memc_rgb_quantise")
+            frames, _flows, _filters, _occlusions = run_model(model, x, autocast)
+            mid = frames[which][:, :, top:top + h, left:left + w]
+            Q = VL if mid.dtype in (torch.float16, torch.bfloat16) else V
+            ok(Q.rgb_quantise(mid, rec), "memc_rgb_quantise")
             out = torch.empty((n, 2, fb), dtype=torch.uint8, device=device)
             for k in range(n):                                      # the file's order: frame i, then the result
                 ok(V.i420_encode(rgb_a[k], 1, h, w, out[k, 0]), "memc_i420_encode")
@@ -229,19 +238,24 @@ def _interpolate_yuv_sequence_gpu(model, in_path, out_path, h, w, device, first,
 
 
 def interpolate_yuv_sequence(model, in_path, out_path, h, w, device, first=0, last=100, pairs_per_step=1, which=1,
-                             gpu_io=False, ssim=False):
+                             gpu_io=False, ssim=False, dtype=None, autocast=None):
     """The demo loop: for i = first, first + 2, ...: frames i and i + 2 in, the interpolated frame i + 1 out
     (out_path receives frame i, then the interpolated frame), scored against the file's own frame i + 1.
     pairs_per_step > 1 batches that many independent pairs through the network at once (same results: every operator
     of the path is per frame pair).  Returns the list of (index of the interpolated frame, mean |dY|, PSNR); with
     ssim=True every tuple gains a fourth element, the SSIM of the two luma planes (luma_ssim).
     gpu_io=True (a CUDA device) decodes, quantises, encodes and scores on the device instead of in numpy on the host:
-    the same bytes, but for Y samples whose float64 sum depends on its order (one level at 0.034 % of the RGB triples)."""
+    the same bytes, but for Y samples whose float64 sum depends on its order (one level at 0.034 % of the RGB triples).
+    dtype=torch.float16 / torch.bfloat16: the planes handed to the model are (float32(byte) / 255).to(dtype), padded in that
+    dtype (the caller has cast the model: model.to(dtype)); autocast=torch.float16 / torch.bfloat16: the model runs inside
+    torch.autocast on float32 planes.  The two exclude each other (ValueError; any other dtype: TypeError -- both before a
+    file is opened).  The result is widened to float32 before it is quantised, on either route."""
+    from .inference import check_precision, interpolate_pairs
+    half = check_precision(dtype, autocast)
     if gpu_io:
         return _interpolate_yuv_sequence_gpu(model, in_path, out_path, h, w, device, first, last, pairs_per_step, which,
-                                             ssim)
+                                             ssim, half, autocast)
     import torch
-    from .inference import interpolate_pairs
     reader, writer = Yuv420Reader(in_path, h, w, to_rgb=True), Yuv420Writer(out_path, from_rgb=True)
     scores = []
     try:
@@ -261,8 +275,12 @@ def interpolate_yuv_sequence(model, in_path, out_path, h, w, device, first=0, la
 
             def to_tensor(frames):
                 x = np.stack([np.transpose(f, (2, 0, 1)) for f in frames]).astype(np.float32) / 255.0
-                return torch.from_numpy(x).to(device)
-            mid = interpolate_pairs(model, to_tensor([a for _, a, _ in batch]), to_tensor([b for _, _, b in batch]), which)
+                x = torch.from_numpy(x).to(device)
+                return x if half is None else x.to(half)
+            mid = interpolate_pairs(model, to_tensor([a for _, a, _ in batch]), to_tensor([b for _, _, b in batch]), which,
+                                    dtype=half, autocast=autocast)
+            if mid.dtype in (torch.float16, torch.bfloat16):
+                mid = mid.float()                          # numpy has no bfloat16; the widening is exact
             mid = np.round(255.0 * mid.clamp(0.0, 1.0).cpu().numpy()).astype(np.uint8)
             for k, (i, a, _b) in enumerate(batch):
                 rec = np.transpose(mid[k], (1, 2, 0))

@@ -5,12 +5,14 @@ frames of a planar YUV 4:2:0 file from its even ones and score them against the 
     python tools/demo_hd720p.py --input clip_1280x720.yuv --output clip_interp.yuv [--height 720 --width 1280]
                                 [--model MEMC_Net_star --weights best.pth --align-corners] [--first 0 --last 100]
                                 [--pairs-per-step 4] [--gpu-io] [--ssim]
+                                [--precision {fp32,bf16,fp16,autocast-bf16,autocast-fp16}]
 
 Frames i and i + 2 go in (replicate-padded to multiples of 128 like demo_HD720p.py:88-113), the output file receives
 frame i and the interpolated frame i + 1 (demo_HD720p.py:146-149); printed per frame: mean |dY| and PSNR on the 8-bit
 luma planes (:150-167).  --ssim adds the SSIM of the two luma planes (:150-190: skimage's compare_ssim at its defaults) and
 writes <output>_psnr_Y.txt and <output>_ssim_Y.txt, one value per line.  Without --weights the network runs on its random
-initialisation (plumbing check only).
+initialisation (plumbing check only).  --precision runs the network in reduced precision: a cast model (bf16, fp16; with
+--gpu-io the planes are decoded and quantised by libmemc_hip_video_lp.so) or a float32 model under torch.autocast.
 Needs a GPU: the operators have no CPU path.
 """
 import argparse
@@ -42,6 +44,10 @@ def main(argv=None):
     ap.add_argument("--ssim", action="store_true",
                     help="also score SSIM on the luma planes (with --gpu-io: libmemc_hip_ssim.so) and write <output>_psnr_Y.txt "
                          "and <output>_ssim_Y.txt")
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "fp16", "autocast-bf16", "autocast-fp16"],
+                    help="fp32 (default): as ever.  bf16 / fp16: the model is cast after its weights are loaded and fed planes of "
+                         "that dtype -- bf16 is the cast mode to prefer, an fp16 cast can overflow in the dense layers.  "
+                         "autocast-bf16 / autocast-fp16: the float32 model runs inside torch.autocast on float32 planes")
     a = ap.parse_args(argv)
 
     import torch
@@ -54,9 +60,15 @@ def main(argv=None):
         state = torch.load(a.weights, map_location="cpu")
         net.load_state_dict(state.get("state_dict", state), strict=True)
     net = net.to(dev).eval()
+    half = {"bf16": torch.bfloat16, "fp16": torch.float16}
+    dtype = half.get(a.precision)
+    autocast = half.get(a.precision[len("autocast-"):]) if a.precision.startswith("autocast-") else None
+    if dtype is not None:
+        net = net.to(dtype)
     scores = networks.interpolate_yuv_sequence(net, a.input, a.output, a.height, a.width, dev, first=a.first, last=a.last,
                                                pairs_per_step=a.pairs_per_step, which=a.save_which, gpu_io=a.gpu_io,
-                                               **(dict(ssim=True) if a.ssim else {}))
+                                               **(dict(ssim=True) if a.ssim else {}),
+                                               **(dict(dtype=dtype, autocast=autocast) if a.precision != "fp32" else {}))
     for s in scores:
         print("frame %4d  mean|dY| %.4f  PSNR %.3f dB" % s[:3] + ("  SSIM %.6f" % s[3] if a.ssim else ""))
     if scores:

@@ -4,12 +4,14 @@ scene directory, interpolate the frame between frame10.png and frame11.png and s
 
     python tools/demo_middlebury.py --data other-data --gt other-gt-interp --output results
                                     [--model MEMC_Net_star --weights best.pth --align-corners] [--save-which 1]
+                                    [--precision {fp32,bf16,fp16,autocast-bf16,autocast-fp16}]
 
 Each pair is replicate-padded to multiples of 128 like demo_MiddleBury.py:98-117 and cropped back; results/<scene>/ receives
 frame10i11.png and, where ground truth exists, the difference picture 128 + rec - gt (named after the scene's mean
 absolute error, :179); printed per scene: mean absolute RGB error and PSNR on the 8-bit pictures (:164-172).  PNG files
 are read and written by networks/png_io.py (8 bits per sample, non-interlaced).  Without --weights the network runs on
-its random initialisation (plumbing check only).  Needs a GPU: the operators have no CPU path.
+its random initialisation (plumbing check only).  --precision runs the network in reduced precision: a cast model (bf16,
+fp16) or a float32 model under torch.autocast.  Needs a GPU: the operators have no CPU path.
 """
 import argparse
 import os
@@ -31,6 +33,10 @@ def main(argv=None):
     ap.add_argument("--align-corners", action="store_true",
                     help="bilinear upsampling as PyTorch 0.2 did it: what the published checkpoints were trained with")
     ap.add_argument("--save-which", type=int, default=1, choices=[0, 1], help="0: blended, 1: rectified (the demos' save_which)")
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "fp16", "autocast-bf16", "autocast-fp16"],
+                    help="fp32 (default): as ever.  bf16 / fp16: the model is cast after its weights are loaded and fed planes of "
+                         "that dtype -- bf16 is the cast mode to prefer, an fp16 cast can overflow in the dense layers.  "
+                         "autocast-bf16 / autocast-fp16: the float32 model runs inside torch.autocast on float32 planes")
     a = ap.parse_args(argv)
 
     import torch
@@ -53,8 +59,14 @@ def main(argv=None):
             print("checkpoint: %d entries loaded, %d not in the model (%s...), %d of the model not in the checkpoint (%s...)" % (
                 len(kept), len(skipped), ", ".join(skipped[:3]), len(missing), ", ".join(missing[:3])))
     net = net.to(dev).eval()
+    half = {"bf16": torch.bfloat16, "fp16": torch.float16}
+    dtype = half.get(a.precision)
+    autocast = half.get(a.precision[len("autocast-"):]) if a.precision.startswith("autocast-") else None
+    if dtype is not None:
+        net = net.to(dtype)
     os.makedirs(a.output, exist_ok=True)
-    results = networks.interpolate_png_tree(net, a.data, a.output, dev, gt_dir=a.gt or None, which=a.save_which)
+    results = networks.interpolate_png_tree(net, a.data, a.output, dev, gt_dir=a.gt or None, which=a.save_which,
+                                           **(dict(dtype=dtype, autocast=autocast) if a.precision != "fp32" else {}))
     scored = [r for r in results if r[1] is not None]
     for scene, err, psnr in results:
         if err is None:
