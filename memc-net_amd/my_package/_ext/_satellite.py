@@ -1,6 +1,6 @@
-"""What the ctypes bindings of the seven warp libraries among the ten satellites share (my_lib_lp, my_lib_lp_grad,
-my_lib_blend_grad, my_lib_mx, my_lib_mx_grad, my_lib_mx_blend_grad, my_lib_lp_blend_grad; my_lib_video, my_lib_ssim and
-my_lib_video_lp take planes, not NCHW descriptors, and bind themselves): the tensor descriptor, the dtype codes and one loader.  Importing this
+"""What the ctypes bindings of the seven warp libraries among the eleven satellites share (my_lib_lp, my_lib_lp_grad,
+my_lib_blend_grad, my_lib_mx, my_lib_mx_grad, my_lib_mx_blend_grad, my_lib_lp_blend_grad; my_lib_video, my_lib_ssim,
+my_lib_video_lp and my_lib_still take planes, not NCHW descriptors, and bind themselves): the tensor descriptor, the dtype codes and one loader.  Importing this
 loads nothing."""
 import ctypes
 import os

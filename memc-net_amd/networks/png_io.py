@@ -135,17 +135,30 @@ def rgb_scores(rec_rgb, gt_rgb):
     return err, psnr, (diff.astype(np.int64) & 0xFF).astype(np.uint8)
 
 
-def interpolate_png_tree(model, data_dir, out_dir, device, gt_dir=None, first="frame10.png", second="frame11.png",
-                         middle="frame10i11.png", which=1, dtype=None, autocast=None):
-    """For every scene directory of data_dir: first + second in, the interpolated middle frame out (out_dir/<scene>/),
-    scored against gt_dir/<scene>/<middle> where that exists.  Returns [(scene, mean abs error, PSNR)] (None, None
-    without ground truth).  Scenes that are not three-channel are skipped, as the reference skips them.
-    dtype / autocast: interpolate_pairs' (a cast model, or torch.autocast around a float32 one), checked before a file is read;
-    a half result is widened to float32 before it is rounded."""
-    import torch
-    from .inference import check_precision, interpolate_pairs
-    check_precision(dtype, autocast)
-    results = []
+def rgb_scores_from_sums(sum_abs, sum_sq, samples):
+    """rgb_scores' two numbers (err, psnr) from the integer sums of |rec - gt| and (rec - gt)^2 over a picture of `samples`
+    samples (3 h w), with its cap of 100.  The same floats as rgb_scores for the same pictures: both sums are integers below
+    2^53 (at most 255^2 * 3 * 32768^2 < 2^48), so numpy's float64 sums of the integer-valued samples are exact whatever their
+    order, and either way one division by the sample count rounds once."""
+    err = float(int(sum_abs)) / samples
+    mse = float(int(sum_sq)) / samples
+    psnr = 100.0 if mse == 0 else min(100.0, float(20.0 * np.log10(255.0 / np.sqrt(mse))))
+    return err, psnr
+
+
+def rgb_ssim(rec_rgb, gt_rgb):
+    """SSIM of two 8-bit RGB pictures [h, w, 3] the way the reference's other picture demo reports it (demo_Vimeo_VE.py:168,
+    compare_ssim(..., multichannel=True) at its defaults): the mean over the three channels of the SSIM of the channel
+    planes (yuv_io.ssim_from_planes).  ValueError for a picture with h or w below 7."""
+    from .yuv_io import ssim_from_planes
+    rec, gt = np.asarray(rec_rgb), np.asarray(gt_rgb)
+    if rec.ndim != 3 or rec.shape[2] != 3 or rec.shape != gt.shape:
+        raise ValueError("expected two [h, w, 3] pictures of one shape, got %s and %s" % (rec.shape, gt.shape))
+    return float(np.mean([ssim_from_planes(rec[:, :, c], gt[:, :, c]) for c in range(3)]))
+
+
+def _usable_scenes(data_dir, first, second):
+    """(scene, first frame, second frame) of every scene directory that has both files and three channels, in sorted order"""
     for scene in sorted(os.listdir(data_dir)):
         a_path, b_path = os.path.join(data_dir, scene, first), os.path.join(data_dir, scene, second)
         if not (os.path.isfile(a_path) and os.path.isfile(b_path)):
@@ -155,25 +168,160 @@ def interpolate_png_tree(model, data_dir, out_dir, device, gt_dir=None, first="f
             raise ValueError("%s: the two frames differ in size (%s, %s)" % (scene, a.shape, b.shape))
         if a.ndim != 3 or a.shape[2] != 3:
             continue
+        yield scene, a, b
 
-        def to_tensor(img):
-            return torch.from_numpy(np.transpose(img, (2, 0, 1)).astype(np.float32) / 255.0).unsqueeze(0).to(device)
-        mid = interpolate_pairs(model, to_tensor(a), to_tensor(b), which, dtype=dtype, autocast=autocast)
-        if mid.dtype in (torch.float16, torch.bfloat16):
-            mid = mid.float()                              # numpy has no bfloat16; the widening is exact
-        rec = np.round(255.0 * mid.clamp(0.0, 1.0)[0].cpu().numpy()).astype(np.uint8)
-        rec = np.ascontiguousarray(np.transpose(rec, (1, 2, 0)))
+
+def _scene_batches(scenes, scenes_per_step):
+    """consecutive scenes of one (h, w), at most scenes_per_step of them, as lists"""
+    batch = []
+    for item in scenes:
+        if batch and item[1].shape != batch[0][1].shape:
+            yield batch
+            batch = []
+        batch.append(item)
+        if len(batch) == scenes_per_step:                  # full: it runs before the next scene's files are read
+            yield batch
+            batch = []
+    if batch:
+        yield batch
+
+
+def _read_gt(gt_dir, scene, middle):
+    """the scene's ground truth (RGBA cut to RGB), or None where there is none"""
+    gt_path = os.path.join(gt_dir, scene, middle) if gt_dir else None
+    if not (gt_path and os.path.isfile(gt_path)):
+        return None
+    gt = read_png(gt_path)
+    if gt.ndim == 3 and gt.shape[2] == 4:
+        gt = gt[:, :, :3]
+    return gt
+
+
+def _diff_path(out_dir, scene, middle, err):
+    stem = middle[:-4] if middle.lower().endswith(".png") else middle
+    return os.path.join(out_dir, scene, "%s_diff%.4f.png" % (stem, err))
+
+
+def _png_batch_host(model, batch, out_dir, device, gt_dir, middle, which, dtype, autocast, ssim):
+    """one batch of interpolate_png_tree with the pixel work in numpy on the host"""
+    import torch
+    from .inference import interpolate_pairs
+
+    def to_tensor(imgs):
+        x = np.stack([np.transpose(img, (2, 0, 1)) for img in imgs])
+        return torch.from_numpy(x.astype(np.float32) / 255.0).to(device)
+    mid = interpolate_pairs(model, to_tensor([a for _, a, _ in batch]), to_tensor([b for _, _, b in batch]), which,
+                            dtype=dtype, autocast=autocast)
+    if mid.dtype in (torch.float16, torch.bfloat16):
+        mid = mid.float()                                  # numpy has no bfloat16; the widening is exact
+    recs = np.round(255.0 * mid.clamp(0.0, 1.0).cpu().numpy()).astype(np.uint8)
+    results = []
+    for k, (scene, _a, _b) in enumerate(batch):
+        rec = np.ascontiguousarray(np.transpose(recs[k], (1, 2, 0)))
         os.makedirs(os.path.join(out_dir, scene), exist_ok=True)
         write_png(os.path.join(out_dir, scene, middle), rec)
-        gt_path = os.path.join(gt_dir, scene, middle) if gt_dir else None
-        if gt_path and os.path.isfile(gt_path):
-            gt = read_png(gt_path)
-            if gt.ndim == 3 and gt.shape[2] == 4:
-                gt = gt[:, :, :3]
+        gt = _read_gt(gt_dir, scene, middle)
+        if gt is not None:
             err, psnr, diff = rgb_scores(rec, gt)
-            stem = middle[:-4] if middle.lower().endswith(".png") else middle
-            write_png(os.path.join(out_dir, scene, "%s_diff%.4f.png" % (stem, err)), diff)
-            results.append((scene, err, psnr))
+            write_png(_diff_path(out_dir, scene, middle, err), diff)
+            results.append((scene, err, psnr) + ((rgb_ssim(rec, gt),) if ssim else ()))
         else:
-            results.append((scene, None, None))
+            results.append((scene, None, None) + ((None,) if ssim else ()))
+    return results
+
+
+def _png_batch_gpu(model, batch, out_dir, device, gt_dir, middle, which, half, autocast, ssim):
+    """one batch of interpolate_png_tree with the pixel work on the device (my_package._ext.my_lib_still, include/
+    memc_still.h): the raw bytes of both frames and of the ground truth go up; decode writes straight into the padded
+    network input; the quantised crop of the result is scored against the ground truth of the scenes that have one; the
+    result bytes, the difference pictures and the integer sums come down.  ssim=True: one memc_ssim_u8 call on the 3 m
+    channel planes of the m scored scenes (my_package._ext.my_lib_ssim); its doubles share the sums' buffer."""
+    import torch
+    import my_package._ext.my_lib_still as S
+    from .inference import pad_amounts, run_model
+
+    def ok(code, what):
+        if code != 0:
+            raise RuntimeError("%s failed its checks (return code %d)" % (what, code))
+
+    n, (h, w, _c) = len(batch), batch[0][1].shape
+    gts = [_read_gt(gt_dir, scene, middle) for scene, _a, _b in batch]
+    for (scene, _a, _b), gt in zip(batch, gts):
+        if gt is not None and gt.shape != (h, w, 3):
+            raise ValueError("%s: the ground truth's shape %s is not the frames' %s" % (scene, gt.shape, (h, w, 3)))
+    scored = [k for k in range(n) if gts[k] is not None]
+    m = len(scored)
+    left, right, top, bottom = pads = pad_amounts(h, w)
+    raw = np.stack([a for _, a, _ in batch] + [b for _, _, b in batch] + [gts[k] for k in scored])
+    raw = torch.from_numpy(np.ascontiguousarray(raw)).to(device)          # [first | second | ground truth], uint8
+    x = torch.empty((2, n, 3, h + top + bottom, w + left + right), dtype=torch.float32 if half is None else half,
+                    device=device)
+    ok(S.rgb8_decode(raw[:n], x[0], pads), "memc_rgb8_decode")
+    ok(S.rgb8_decode(raw[n:2 * n], x[1], pads), "memc_rgb8_decode")
+    frames, _flows, _filters, _occlusions = run_model(model, x, autocast)
+    mid = frames[which][:, :, top:top + h, left:left + w]
+    out = torch.empty((n + m, h, w, 3), dtype=torch.uint8, device=device)  # [results | difference pictures]
+    ok(S.rgb8_quantise(mid, out[:n]), "memc_rgb8_quantise")
+    down = None
+    if m:
+        rec = out[:n] if m == n else out[:n].index_select(0, torch.tensor(scored, device=device))
+        down = torch.empty(m * (5 if ssim else 2), dtype=torch.int64, device=device)      # [m, 2] sums | 3 m doubles
+        work = torch.empty(S.rgb8_score_workspace_bytes(m, h, w), dtype=torch.uint8, device=device)
+        ok(S.rgb8_score(rec, raw[2 * n:], down[:2 * m].view(m, 2), work, diff=out[n:]), "memc_rgb8_score")
+        if ssim:
+            import my_package._ext.my_lib_ssim as SS
+            pa, pb = (t.permute(0, 3, 1, 2).contiguous().view(3 * m, h, w) for t in (rec, raw[2 * n:]))
+            work = torch.empty(SS.ssim_workspace_bytes(3 * m, h, w), dtype=torch.uint8, device=device)
+            ok(SS.ssim_u8(pa, pb, down[2 * m:].view(torch.float64), work), "memc_ssim_u8")
+        down = down.cpu().numpy()
+    out = out.cpu().numpy()
+    results = []
+    for k, (scene, _a, _b) in enumerate(batch):
+        os.makedirs(os.path.join(out_dir, scene), exist_ok=True)
+        write_png(os.path.join(out_dir, scene, middle), out[k])
+        if gts[k] is None:
+            results.append((scene, None, None) + ((None,) if ssim else ()))
+            continue
+        j = scored.index(k)
+        sums = down[2 * j:2 * j + 2].view(np.uint64)
+        err, psnr = rgb_scores_from_sums(sums[0], sums[1], 3 * h * w)
+        write_png(_diff_path(out_dir, scene, middle, err), out[n + j])
+        score = (scene, err, psnr)
+        results.append(score + (float(np.mean(down[2 * m + 3 * j:2 * m + 3 * j + 3].view(np.float64))),) if ssim else score)
+    return results
+
+
+def interpolate_png_tree(model, data_dir, out_dir, device, gt_dir=None, first="frame10.png", second="frame11.png",
+                         middle="frame10i11.png", which=1, dtype=None, autocast=None, gpu_io=False, scenes_per_step=1,
+                         ssim=False):
+    """For every scene directory of data_dir: first + second in, the interpolated middle frame out (out_dir/<scene>/),
+    scored against gt_dir/<scene>/<middle> where that exists.  Returns [(scene, mean abs error, PSNR)] (None, None
+    without ground truth).  Scenes that are not three-channel are skipped, as the reference skips them.
+    dtype / autocast: interpolate_pairs' (a cast model, or torch.autocast around a float32 one), checked before a file is read;
+    a half result is widened to float32 before it is rounded.
+    scenes_per_step=N: consecutive usable scenes (sorted order) of one (h, w) go through the network as one batch of at most
+    N; a batch ends when it holds N scenes, when the next usable scene has another size, or at the end.  Skipped scenes
+    neither enter nor end a batch.  The results keep the sorted order and are those of N = 1 (every operator of the path is
+    per frame pair).  N < 1: ValueError, before a file is read.
+    gpu_io=True (a CUDA device; otherwise ValueError, before a file is read): the float conversion, the padding, the
+    quantisation, the error sums and the difference picture run on the device (libmemc_hip_still.so, include/memc_still.h)
+    instead of in numpy on the host: the same bytes and the same floats.
+    ssim=True: every tuple gains a fourth element, the RGB SSIM against the ground truth (rgb_ssim; None without ground
+    truth); ValueError for a picture with h or w below 7."""
+    import torch
+    from .inference import check_precision
+    half = check_precision(dtype, autocast)
+    if scenes_per_step < 1:
+        raise ValueError("scenes_per_step: expected at least 1, got %r" % (scenes_per_step,))
+    if gpu_io and torch.device(device).type != "cuda":
+        raise ValueError("gpu_io=True needs a CUDA (HIP) device, got %s" % (device,))
+    results = []
+    for batch in _scene_batches(_usable_scenes(data_dir, first, second), scenes_per_step):
+        if ssim and min(batch[0][1].shape[:2]) < 7:
+            raise ValueError("%s: SSIM's 7 x 7 window needs h and w of at least 7, got %dx%d" % (
+                batch[0][0], batch[0][1].shape[1], batch[0][1].shape[0]))
+        if gpu_io:
+            results += _png_batch_gpu(model, batch, out_dir, torch.device(device), gt_dir, middle, which, half, autocast, ssim)
+        else:
+            results += _png_batch_host(model, batch, out_dir, device, gt_dir, middle, which, dtype, autocast, ssim)
     return results

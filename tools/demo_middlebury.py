@@ -5,13 +5,19 @@ scene directory, interpolate the frame between frame10.png and frame11.png and s
     python tools/demo_middlebury.py --data other-data --gt other-gt-interp --output results
                                     [--model MEMC_Net_star --weights best.pth --align-corners] [--save-which 1]
                                     [--precision {fp32,bf16,fp16,autocast-bf16,autocast-fp16}]
+                                    [--gpu-io] [--scenes-per-step N] [--ssim]
+                                    [--first im1.png --second im3.png --middle im2.png]
 
 Each pair is replicate-padded to multiples of 128 like demo_MiddleBury.py:98-117 and cropped back; results/<scene>/ receives
 frame10i11.png and, where ground truth exists, the difference picture 128 + rec - gt (named after the scene's mean
 absolute error, :179); printed per scene: mean absolute RGB error and PSNR on the 8-bit pictures (:164-172).  PNG files
 are read and written by networks/png_io.py (8 bits per sample, non-interlaced).  Without --weights the network runs on
 its random initialisation (plumbing check only).  --precision runs the network in reduced precision: a cast model (bf16,
-fp16) or a float32 model under torch.autocast.  Needs a GPU: the operators have no CPU path.
+fp16) or a float32 model under torch.autocast.  --gpu-io does the pixel work around the network (float conversion, padding,
+quantisation, error sums, difference picture) on the device: the same bytes and numbers; --scenes-per-step N sends up to N
+consecutive scenes of one size through the network at once; --ssim adds the RGB SSIM (the mean over the three channels, as
+demo_Vimeo_VE.py:168 reports it) as a third column.  --first / --second / --middle name the files of a scene, so that a
+Vimeo-90K tree (im1.png, im3.png, im2.png) runs as it is.  Needs a GPU: the operators have no CPU path.
 """
 import argparse
 import os
@@ -37,6 +43,14 @@ def main(argv=None):
                     help="fp32 (default): as ever.  bf16 / fp16: the model is cast after its weights are loaded and fed planes of "
                          "that dtype -- bf16 is the cast mode to prefer, an fp16 cast can overflow in the dense layers.  "
                          "autocast-bf16 / autocast-fp16: the float32 model runs inside torch.autocast on float32 planes")
+    ap.add_argument("--gpu-io", action="store_true",
+                    help="frame I/O and scores on the device (libmemc_hip_still.so) instead of in numpy on the host")
+    ap.add_argument("--scenes-per-step", type=int, default=1, metavar="N",
+                    help="consecutive scenes of one size that go through the network as one batch (default 1)")
+    ap.add_argument("--ssim", action="store_true", help="also report the RGB SSIM (mean over the three channels)")
+    ap.add_argument("--first", default="frame10.png", help="file name of a scene's first frame")
+    ap.add_argument("--second", default="frame11.png", help="file name of a scene's second frame")
+    ap.add_argument("--middle", default="frame10i11.png", help="file name of the frame in between (output and ground truth)")
     a = ap.parse_args(argv)
 
     import torch
@@ -65,17 +79,24 @@ def main(argv=None):
     if dtype is not None:
         net = net.to(dtype)
     os.makedirs(a.output, exist_ok=True)
-    results = networks.interpolate_png_tree(net, a.data, a.output, dev, gt_dir=a.gt or None, which=a.save_which,
-                                           **(dict(dtype=dtype, autocast=autocast) if a.precision != "fp32" else {}))
+    kw = dict(dtype=dtype, autocast=autocast) if a.precision != "fp32" else {}
+    for name, value, default in (("first", a.first, "frame10.png"), ("second", a.second, "frame11.png"),
+                                 ("middle", a.middle, "frame10i11.png"), ("gpu_io", a.gpu_io, False),
+                                 ("scenes_per_step", a.scenes_per_step, 1), ("ssim", a.ssim, False)):
+        if value != default:                               # a default run makes the call it always made
+            kw[name] = value
+    results = networks.interpolate_png_tree(net, a.data, a.output, dev, gt_dir=a.gt or None, which=a.save_which, **kw)
     scored = [r for r in results if r[1] is not None]
-    for scene, err, psnr in results:
-        if err is None:
-            print("%-16s written (no ground truth)" % scene)
+    what = "interpolation error / PSNR / SSIM" if a.ssim else "interpolation error / PSNR"
+    fmt = " / ".join(["%.4f"] * (3 if a.ssim else 2))
+    for r in results:
+        if r[1] is None:
+            print("%-16s written (no ground truth)" % r[0])
         else:
-            print("%-16s interpolation error / PSNR : %.4f / %.4f" % (scene, err, psnr))
+            print(("%-16s " + what + " : " + fmt) % tuple(r))
     if scored:
-        print("The average interpolation error / PSNR for all %d images are : %.4f / %.4f" % (
-            len(scored), sum(r[1] for r in scored) / len(scored), sum(r[2] for r in scored) / len(scored)))
+        print(("The average " + what + " for all %d images are : " + fmt) % (
+            (len(scored),) + tuple(sum(r[k] for r in scored) / len(scored) for k in range(1, len(scored[0])))))
 
 
 if __name__ == "__main__":

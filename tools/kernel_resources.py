@@ -23,7 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hi
          "-I" + os.path.join(ROOT, "include"), "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null"]
 SOURCES = ["filter_interpolation.hip", "fi_bwd_c3.hip", "fi_bwd_cn.hip", "interpolation.hip", "flow_projection.hip",
            "flow_prologue.hip", "calibration.hip", "fi_blend_bwd_c3.hip", "mx_filter_interpolation.hip",
-           "mx_fi_bwd_c3.hip", "mx_fi_blend_bwd_c3.hip", "lp_fi_blend_bwd_c3.hip", "ssim.hip", "lp_video_io.hip"]
+           "mx_fi_bwd_c3.hip", "mx_fi_blend_bwd_c3.hip", "lp_fi_blend_bwd_c3.hip", "ssim.hip", "lp_video_io.hip", "still_io.hip"]
 
 _KEYS = {"Function Name": "name", "TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs",
          "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
