@@ -1,6 +1,7 @@
 // still_io.hip -- the frame I/O and the scores of the still-image demo loop (networks/png_io.py) for gfx950: the kernels and
-// the C ABI of libmemc_hip_still.so (include/memc_still.h).  One translation unit, nothing shared with the other libraries:
-// the small lane helpers below are this unit's own copies of video_io.hip's and lp_video_io.hip's.
+// the C ABI of libmemc_hip_still.so (include/memc_still.h).  One translation unit; no object and no symbol shared with the
+// other libraries.  The storage tags, the lane scheme, the wave sum, the final pass's body and the host checks are
+// memc_frame_io.hpp's, shared as text with video_io.hip and lp_video_io.hip; nothing of the I420 arithmetic comes with them.
 //
 // Three streaming kernels and a final pass, no LDS anywhere in this file:
 //   rgb8_decode<T>    a gather over the PADDED extent: lane (frame, padded row, quad of padded columns) clamps its source
@@ -16,61 +17,16 @@
 // Memory: heights and widths are odd as often as not, so a row of the bytes and a frame of them start on any byte and a row
 // of a plane on any element: bytes move through vector types of alignment 1, four T through a vector type of T's alignment
 // (the queues run in unaligned-access mode, as for video_io.hip's f32x4u).
-#include <hip/hip_runtime.h>
-
+#include "memc_frame_io.hpp"
 #include "memc_still.h"
 
 #pragma clang fp contract(off)
 
 namespace memc {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef f32x4 f32x4u __attribute__((aligned(4)));
-typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
-typedef u16x4 u16x4u __attribute__((aligned(2)));
-typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
-typedef u32x3 u32x3u __attribute__((aligned(1)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x4 u32x4u __attribute__((aligned(1)));
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxDim = 32768;
 constexpr int kMaxScoreBlocks = MEMC_STILL_SCORE_MAX_BLOCKS;      // workgroups per frame of rgb8_partial
 constexpr int kMaxScoreFrames = MEMC_STILL_SCORE_MAX_FRAMES;      // the frame is the grid's y
 constexpr int kTrip = 16;                                         // samples of one lane's trip
-constexpr int kFloat32 = 0, kFloat16 = 1, kBFloat16 = 2;          // memc_dtype's values
-
-struct F32 {
-    typedef float elem;
-    typedef f32x4 vec;
-    typedef f32x4u vecu;
-    static __device__ __forceinline__ float narrow(float x) { return x; }
-    static __device__ __forceinline__ float widen(float b) { return b; }
-};
-
-// IEEE binary16: the compiler's conversions (v_cvt_f16_f32 rounds to nearest even; widening is exact)
-struct F16 {
-    typedef uint16_t elem;
-    typedef u16x4 vec;
-    typedef u16x4u vecu;
-    static __device__ __forceinline__ uint16_t narrow(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }
-    static __device__ __forceinline__ float widen(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
-};
-
-// bfloat16: the upper half of a float32; round to nearest even on the 16 bits dropped, NaN kept quiet
-struct BF16 {
-    typedef uint16_t elem;
-    typedef u16x4 vec;
-    typedef u16x4u vecu;
-    static __device__ __forceinline__ uint16_t narrow(float x)
-    {
-        const uint32_t u = __builtin_bit_cast(uint32_t, x);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);
-        return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    }
-    static __device__ __forceinline__ float widen(uint16_t b) { return __builtin_bit_cast(float, (uint32_t)b << 16); }
-};
 
 // rintf(255 clamp(x, 0, 1)): numpy's round (ties to even) of the float32 product; NaN -> 0 (fmaxf returns the other operand)
 __device__ __forceinline__ uint8_t quantise(float x) { return (uint8_t)(int)rintf(255.0f * fminf(fmaxf(x, 0.0f), 1.0f)); }
@@ -121,18 +77,6 @@ struct Run16 : Bytes<4> {
     }
     __device__ __forceinline__ void store(uint8_t *p) const { *reinterpret_cast<u32x4u *>(p) = u32x4{w[0], w[1], w[2], w[3]}; }
 };
-
-// lane -> (frame, row, first column of the quad) of an extent of `rows` x `qpr` quads per frame; false past the end
-__device__ __forceinline__ bool quad_of_lane(int frames, int rows, int qpr, int &f, int &y, int &x0)
-{
-    const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (idx >= (int64_t)frames * rows * qpr) return false;
-    const int64_t row = idx / qpr;
-    x0 = 4 * (int)(idx - row * qpr);
-    f = (int)(row / rows);
-    y = (int)(row - (int64_t)f * rows);
-    return true;
-}
 
 template <typename T>
 __global__ __launch_bounds__(kThreads) void rgb8_decode(const uint8_t *__restrict__ rgb, int frames, int h, int w,
@@ -200,12 +144,6 @@ __global__ __launch_bounds__(kThreads) void rgb8_quantise(const typename T::elem
     else q.store_bytes(o, 3 * count);
 }
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;                                      // lane 0 holds the wave's sum
-}
-
 // grid (blocks per frame, frames); partial[((f * gridDim.x + block) * kWaves + wave) * 2 + {0, 1}]; n = 3 h w samples a frame
 __global__ __launch_bounds__(kThreads) void rgb8_partial(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b,
                                                          int64_t n, uint8_t *__restrict__ diff,
@@ -254,18 +192,7 @@ __global__ __launch_bounds__(kThreads) void rgb8_partial(const uint8_t *__restri
 __global__ __launch_bounds__(64) void rgb8_final(const unsigned long long *__restrict__ partial, int n,
                                                  unsigned long long *__restrict__ sums)
 {
-    const unsigned long long *p = partial + (int64_t)blockIdx.x * n * 2;
-    unsigned long long sabs = 0, ssq = 0;
-    for (int i = threadIdx.x; i < n; i += 64) {
-        sabs += p[2 * i];
-        ssq += p[2 * i + 1];
-    }
-    sabs = wave_sum(sabs);
-    ssq = wave_sum(ssq);
-    if (threadIdx.x == 0) {
-        sums[2 * blockIdx.x] = sabs;
-        sums[2 * blockIdx.x + 1] = ssq;
-    }
+    add_partials(partial, n, sums);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
@@ -274,23 +201,12 @@ static bool dims_ok(int h, int w) { return h > 0 && w > 0 && h <= kMaxDim && w <
 
 static bool dtype_ok(int dtype) { return dtype == kFloat32 || dtype == kFloat16 || dtype == kBFloat16; }
 
-static bool pad_ok(int p) { return p >= 0 && p <= kMaxDim; }
-
 static int score_blocks(int h, int w)
 {
     const int64_t trips = ((int64_t)h * w * 3 + kTrip - 1) / kTrip;
     const int64_t blocks = (trips + kThreads - 1) / kThreads;
     return (int)(blocks < kMaxScoreBlocks ? blocks : kMaxScoreBlocks);
 }
-
-// blocks of kThreads lanes for `lanes` lanes; 0 where the grid would not fit
-static unsigned grid_for(int64_t lanes)
-{
-    const int64_t blocks = (lanes + kThreads - 1) / kThreads;
-    return blocks > 0x7fffffffLL ? 0u : (unsigned)blocks;
-}
-
-static int launched() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
 template <typename T>
 static int launch_decode(hipStream_t stream, unsigned grid, const uint8_t *rgb, int frames, int h, int w, void *planes,
@@ -325,12 +241,12 @@ int memc_rgb8_decode(memc_still_stream_t stream, const uint8_t *rgb_u8, int fram
     if (frames < 0) return -1;
     if (!dims_ok(h, w)) return -1;
     if (!dtype_ok(dtype)) return -1;
-    if (!pad_ok(pad_left) || !pad_ok(pad_right) || !pad_ok(pad_top) || !pad_ok(pad_bottom)) return -1;
-    const int hp = h + pad_top + pad_bottom, wp = w + pad_left + pad_right;
-    if (stride_frame <= 0 || stride_c <= 0 || stride_row < wp) return -1;
+    int hp, wp;
+    if (!padded_extent_ok(h, w, pad_left, pad_right, pad_top, pad_bottom, true, stride_frame, stride_c, stride_row, hp, wp))
+        return -1;
     if (frames == 0) return 0;
     if (!rgb_u8 || !planes) return -1;
-    const unsigned grid = grid_for((int64_t)frames * hp * ((wp + 3) / 4));
+    const unsigned grid = quad_grid(frames, hp, wp);
     if (!grid) return -1;
     const hipStream_t s = (hipStream_t)stream;
     if (dtype == kFloat32)
@@ -346,10 +262,10 @@ int memc_rgb8_quantise(memc_still_stream_t stream, const void *planes, int dtype
     if (frames < 0) return -1;
     if (!dims_ok(h, w)) return -1;
     if (!dtype_ok(dtype)) return -1;
-    if (stride_frame <= 0 || stride_c <= 0 || stride_row < w) return -1;
+    if (!strides_ok(stride_frame, stride_c, stride_row, w)) return -1;
     if (frames == 0) return 0;
     if (!planes || !rgb_u8) return -1;
-    const unsigned grid = grid_for((int64_t)frames * h * ((w + 3) / 4));
+    const unsigned grid = quad_grid(frames, h, w);
     if (!grid) return -1;
     const hipStream_t s = (hipStream_t)stream;
     if (dtype == kFloat32) return launch_quantise<F32>(s, grid, planes, stride_frame, stride_c, stride_row, frames, h, w, rgb_u8);

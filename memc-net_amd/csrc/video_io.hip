@@ -1,11 +1,12 @@
 // video_io.hip -- the frame I/O of the HD demo loop (networks/yuv_io.py) for gfx950: the kernels and the C ABI of
-// libmemc_hip_video.so (include/memc_video.h).  One translation unit, nothing shared with the other libraries.
+// libmemc_hip_video.so (include/memc_video.h).  One translation unit; no object and no symbol shared with the other
+// libraries.  The lane scheme, the wave sum and the host checks are memc_frame_io.hpp's, shared as text with lp_video_io.hip
+// and still_io.hip; the quad's bytes and the bodies of the first two kernels are memc_frame_io_i420.hpp's, with lp_video_io.hip.
 //
 // Four streaming byte kernels and a final pass; a lane takes four horizontally adjacent pixels of one row:
-//   i420_decode     a gather over the PADDED extent: lane (frame, padded row, quad of padded columns) clamps its source
-//                   coordinates (replicate padding), decodes, stores float32(byte) / 255 into the three planes and, for the
-//                   pixels inside the frame, the RGB bytes.  Every element has one writer.
-//   rgb_quantise    three float quads in, twelve bytes out.
+//   i420_decode     i420_decode_body.inc on float32 planes: a gather over the PADDED extent that stores float32(byte) / 255
+//                   into the three planes and, for the pixels inside the frame, the RGB bytes.
+//   rgb_quantise    rgb_quantise_body.inc on float32 planes: three float quads in, twelve bytes out.
 //   i420_encode     twelve bytes in, four Y bytes out and, on even rows, two U and two V bytes (even columns).
 //   luma_partial    a workgroup strides over its frame's quads; per lane uint64 sums of |dY| and dY^2, reduced over the wave
 //                   by shuffles; one partial per WAVE goes to the workspace.  luma_final: one wave per frame adds them.
@@ -13,140 +14,28 @@
 // The arithmetic is memc_video_math.hpp's (float64, explicit fma chain, contraction off).
 // Memory: plane offsets inside an I420 buffer and RGB rows have any alignment, so bytes move through vector types of
 // alignment 1 (the queues run in unaligned-access mode, as for memc_tile.hpp's f32x4u) and floats through f32x4u.
-#include <hip/hip_runtime.h>
-
-#include "memc_video_math.hpp"
+#include "memc_frame_io_i420.hpp"
 #include "memc_video.h"
 
 #pragma clang fp contract(off)
 
 namespace memc {
 
-namespace mv = memc_video;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef f32x4 f32x4u __attribute__((aligned(4)));
-typedef uint8_t u8x2 __attribute__((ext_vector_type(2)));
-typedef uint8_t u8x4 __attribute__((ext_vector_type(4)));
-typedef u8x2 u8x2u __attribute__((aligned(1)));
-typedef u8x4 u8x4u __attribute__((aligned(1)));
-typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
-typedef u32x3 u32x3u __attribute__((aligned(1)));
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxDim = 32768;
 constexpr int kMaxScoreBlocks = 1024;      // workgroups per frame of luma_partial
-
-// twelve RGB bytes of four pixels
-union Rgb4 {
-    u32x3 v;
-    uint8_t b[12];
-};
-
-__device__ __forceinline__ void load_rgb4(const uint8_t *p, int count, Rgb4 &q)
-{
-    if (count == 4) {
-        q.v = *reinterpret_cast<const u32x3u *>(p);
-    } else {
-        q.v = u32x3{0u, 0u, 0u};
-        for (int i = 0; i < 3 * count; i++) q.b[i] = p[i];
-    }
-}
-
-__device__ __forceinline__ void store_rgb4(uint8_t *p, int count, const Rgb4 &q)
-{
-    if (count == 4) {
-        *reinterpret_cast<u32x3u *>(p) = q.v;
-    } else {
-        for (int i = 0; i < 3 * count; i++) p[i] = q.b[i];
-    }
-}
-
-// lane -> (frame, row, first column of the quad) of an extent of `rows` x `qpr` quads per frame; false past the end
-__device__ __forceinline__ bool quad_of_lane(int frames, int rows, int qpr, int &f, int &y, int &x0)
-{
-    const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (idx >= (int64_t)frames * rows * qpr) return false;
-    const int64_t row = idx / qpr;
-    x0 = 4 * (int)(idx - row * qpr);
-    f = (int)(row / rows);
-    y = (int)(row - (int64_t)f * rows);
-    return true;
-}
 
 __global__ __launch_bounds__(kThreads) void i420_decode(const uint8_t *__restrict__ i420, int frames, int h, int w,
                                                         uint8_t *__restrict__ rgb, float *__restrict__ planes, int64_t sf,
                                                         int64_t sc, int64_t sr, int pl, int pt, int hp, int wp)
 {
-    int f, yp, xp0;
-    if (!quad_of_lane(frames, hp, (wp + 3) / 4, f, yp, xp0)) return;
-    const int count = min(4, wp - xp0);
-    const int64_t ny = (int64_t)h * w, nc = (int64_t)(h / 2) * (w / 2);
-    const uint8_t *Y = i420 + (int64_t)f * (ny + 2 * nc), *U = Y + ny, *V = U + nc;
-    const int oy = yp - pt, sy = min(max(oy, 0), h - 1);
-    const int ox0 = xp0 - pl;
-    const uint8_t *yrow = Y + (int64_t)sy * w;
-    const int64_t crow = (int64_t)(sy / 2) * (w / 2);
-    const bool inside = ox0 >= 0 && ox0 + 3 < w && count == 4;     // four source columns, none clamped
-
-    uint8_t yb[4];
-    if (inside) {
-        const u8x4 y4 = *reinterpret_cast<const u8x4u *>(yrow + ox0);
-        for (int j = 0; j < 4; j++) yb[j] = y4[j];
-    } else {
-        for (int j = 0; j < 4; j++) yb[j] = yrow[min(max(ox0 + j, 0), w - 1)];     // j >= count: a valid address, unused
-    }
-    Rgb4 q;
-    for (int j = 0; j < 4; j++) {
-        const int sx = min(max(ox0 + j, 0), w - 1);
-        uint8_t px[3];
-        mv::decode_pixel(yb[j], U[crow + sx / 2], V[crow + sx / 2], px);
-        for (int c = 0; c < 3; c++) q.b[3 * j + c] = px[c];
-    }
-    if (planes) {
-        float *o = planes + f * sf + yp * sr + xp0;
-        for (int c = 0; c < 3; c++, o += sc) {
-            if (count == 4) {
-                f32x4 v;
-                for (int j = 0; j < 4; j++) v[j] = (float)q.b[3 * j + c] / 255.0f;
-                *reinterpret_cast<f32x4u *>(o) = v;
-            } else {
-                for (int j = 0; j < count; j++) o[j] = (float)q.b[3 * j + c] / 255.0f;
-            }
-        }
-    }
-    if (rgb && oy >= 0 && oy < h) {
-        uint8_t *o = rgb + (((int64_t)f * h + oy) * w + ox0) * 3;
-        if (inside) {
-            store_rgb4(o, 4, q);
-        } else {
-            for (int j = 0; j < count; j++) {
-                if (ox0 + j < 0 || ox0 + j >= w) continue;
-                for (int c = 0; c < 3; c++) o[3 * j + c] = q.b[3 * j + c];
-            }
-        }
-    }
+    using T = F32;
+#include "i420_decode_body.inc"
 }
 
 __global__ __launch_bounds__(kThreads) void rgb_quantise(const float *__restrict__ planes, int64_t sf, int64_t sc, int64_t sr,
                                                          int frames, int h, int w, uint8_t *__restrict__ rgb)
 {
-    int f, y, x0;
-    if (!quad_of_lane(frames, h, (w + 3) / 4, f, y, x0)) return;
-    const int count = min(4, w - x0);
-    const float *p = planes + f * sf + y * sr + x0;
-    Rgb4 q;
-    q.v = u32x3{0u, 0u, 0u};
-    for (int c = 0; c < 3; c++, p += sc) {
-        if (count == 4) {
-            const f32x4 v = *reinterpret_cast<const f32x4u *>(p);
-            for (int j = 0; j < 4; j++) q.b[3 * j + c] = mv::quantise(v[j]);
-        } else {
-            for (int j = 0; j < count; j++) q.b[3 * j + c] = mv::quantise(p[j]);
-        }
-    }
-    store_rgb4(rgb + (((int64_t)f * h + y) * w + x0) * 3, count, q);
+    using T = F32;
+#include "rgb_quantise_body.inc"
 }
 
 __global__ __launch_bounds__(kThreads) void i420_encode(const uint8_t *__restrict__ rgb, int frames, int h, int w,
@@ -155,7 +44,7 @@ __global__ __launch_bounds__(kThreads) void i420_encode(const uint8_t *__restric
     int f, y, x0;
     if (!quad_of_lane(frames, h, (w + 3) / 4, f, y, x0)) return;
     const int count = min(4, w - x0);              // 4 or 2: w is even
-    Rgb4 q;
+    Rgb4Bytes q;
     load_rgb4(rgb + (((int64_t)f * h + y) * w + x0) * 3, count, q);
     const int64_t ny = (int64_t)h * w, nc = (int64_t)(h / 2) * (w / 2);
     uint8_t *Y = i420 + (int64_t)f * (ny + 2 * nc), *U = Y + ny, *V = U + nc;
@@ -182,12 +71,6 @@ __global__ __launch_bounds__(kThreads) void i420_encode(const uint8_t *__restric
     }
 }
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;                                      // lane 0 holds the wave's sum
-}
-
 // grid (blocks per frame, frames); partial[(f * gridDim.x * kWaves + wave of the frame) * 2 + {0, 1}]
 __global__ __launch_bounds__(kThreads) void luma_partial(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, int h,
                                                          int w, unsigned long long *__restrict__ partial)
@@ -199,7 +82,7 @@ __global__ __launch_bounds__(kThreads) void luma_partial(const uint8_t *__restri
         const int64_t y = i / qpr;
         const int x0 = 4 * (int)(i - y * qpr), count = min(4, w - x0);
         const int64_t o = base + (y * w + x0) * 3;
-        Rgb4 qa, qb;
+        Rgb4Bytes qa, qb;
         load_rgb4(a + o, count, qa);
         load_rgb4(b + o, count, qb);
         for (int j = 0; j < count; j++) {
@@ -222,26 +105,10 @@ __global__ __launch_bounds__(kThreads) void luma_partial(const uint8_t *__restri
 __global__ __launch_bounds__(64) void luma_final(const unsigned long long *__restrict__ partial, int n,
                                                  unsigned long long *__restrict__ sums)
 {
-    const unsigned long long *p = partial + (int64_t)blockIdx.x * n * 2;
-    unsigned long long sabs = 0, ssq = 0;
-    for (int i = threadIdx.x; i < n; i += 64) {
-        sabs += p[2 * i];
-        ssq += p[2 * i + 1];
-    }
-    sabs = wave_sum(sabs);
-    ssq = wave_sum(ssq);
-    if (threadIdx.x == 0) {
-        sums[2 * blockIdx.x] = sabs;
-        sums[2 * blockIdx.x + 1] = ssq;
-    }
+    add_partials(partial, n, sums);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
-
-static bool dims_ok(int frames, int h, int w)
-{
-    return frames >= 0 && h > 0 && w > 0 && !(h & 1) && !(w & 1) && h <= kMaxDim && w <= kMaxDim;
-}
 
 static int score_blocks(int h, int w)
 {
@@ -249,15 +116,6 @@ static int score_blocks(int h, int w)
     const int64_t blocks = (quads + kThreads - 1) / kThreads;
     return (int)(blocks < kMaxScoreBlocks ? blocks : kMaxScoreBlocks);
 }
-
-// blocks of kThreads lanes for `lanes` lanes; 0 where the grid would not fit
-static unsigned grid_for(int64_t lanes)
-{
-    const int64_t blocks = (lanes + kThreads - 1) / kThreads;
-    return blocks > 0x7fffffffLL ? 0u : (unsigned)blocks;
-}
-
-static int launched() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
 }  // namespace memc
 
@@ -273,13 +131,13 @@ int memc_i420_decode(memc_video_stream_t stream, const uint8_t *i420, int frames
 {
     if (!dims_ok(frames, h, w)) return -1;
     if (!planes) pad_left = pad_right = pad_top = pad_bottom = 0;
-    if (pad_left < 0 || pad_right < 0 || pad_top < 0 || pad_bottom < 0) return -1;
-    if (pad_left > kMaxDim || pad_right > kMaxDim || pad_top > kMaxDim || pad_bottom > kMaxDim) return -1;
-    const int hp = h + pad_top + pad_bottom, wp = w + pad_left + pad_right;
-    if (planes && (stride_frame <= 0 || stride_c <= 0 || stride_row < wp)) return -1;
+    int hp, wp;
+    if (!padded_extent_ok(h, w, pad_left, pad_right, pad_top, pad_bottom, planes != nullptr, stride_frame, stride_c, stride_row,
+                          hp, wp))
+        return -1;
     if (frames == 0) return 0;
     if (!i420 || (!rgb_u8 && !planes)) return -1;
-    const unsigned grid = grid_for((int64_t)frames * hp * ((wp + 3) / 4));
+    const unsigned grid = quad_grid(frames, hp, wp);
     if (!grid) return -1;
     hipLaunchKernelGGL(i420_decode, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, i420, frames, h, w, rgb_u8, planes,
                        stride_frame, stride_c, stride_row, pad_left, pad_top, hp, wp);
@@ -290,10 +148,10 @@ int memc_rgb_quantise(memc_video_stream_t stream, const float *planes, int64_t s
                       int64_t stride_row, int frames, int h, int w, uint8_t *rgb_u8)
 {
     if (!dims_ok(frames, h, w)) return -1;
-    if (stride_frame <= 0 || stride_c <= 0 || stride_row < w) return -1;
+    if (!strides_ok(stride_frame, stride_c, stride_row, w)) return -1;
     if (frames == 0) return 0;
     if (!planes || !rgb_u8) return -1;
-    const unsigned grid = grid_for((int64_t)frames * h * ((w + 3) / 4));
+    const unsigned grid = quad_grid(frames, h, w);
     if (!grid) return -1;
     hipLaunchKernelGGL(rgb_quantise, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, planes, stride_frame, stride_c,
                        stride_row, frames, h, w, rgb_u8);
@@ -305,7 +163,7 @@ int memc_i420_encode(memc_video_stream_t stream, const uint8_t *rgb_u8, int fram
     if (!dims_ok(frames, h, w)) return -1;
     if (frames == 0) return 0;
     if (!rgb_u8 || !i420) return -1;
-    const unsigned grid = grid_for((int64_t)frames * h * ((w + 3) / 4));
+    const unsigned grid = quad_grid(frames, h, w);
     if (!grid) return -1;
     hipLaunchKernelGGL(i420_encode, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, rgb_u8, frames, h, w, i420);
     return launched();

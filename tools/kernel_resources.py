@@ -16,14 +16,16 @@ import re
 import subprocess
 import sys
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_diff import make_vars      # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "memc-net_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-munsafe-fp-atomics",
          "-I" + os.path.join(ROOT, "include"), "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null"]
-SOURCES = ["filter_interpolation.hip", "fi_bwd_c3.hip", "fi_bwd_cn.hip", "interpolation.hip", "flow_projection.hip",
-           "flow_prologue.hip", "calibration.hip", "fi_blend_bwd_c3.hip", "mx_filter_interpolation.hip",
-           "mx_fi_bwd_c3.hip", "mx_fi_blend_bwd_c3.hip", "lp_fi_blend_bwd_c3.hip", "ssim.hip", "lp_video_io.hip", "still_io.hip"]
+# every .hip unit of the product library and of the satellite libraries, read from the Makefile: a new library needs no edit here
+SOURCES = [s for s in make_vars(ROOT)["SRCS"] if s.endswith(".hip")] + make_vars(ROOT)["SATELLITES"]
 
 _KEYS = {"Function Name": "name", "TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs",
          "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
