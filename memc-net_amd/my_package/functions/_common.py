@@ -69,9 +69,11 @@ def flow_dtype(flow, payload):
 
 
 def host_widened(apply, like, *args):
-    """The operators without half kernels (FlowProjection, DepthFlowProjection, Interpolation, InterpolationCh):
-    float16 / bfloat16 tensors among `args` are widened to float32 on the host, `apply` (the float32 Function) runs, and
-    the result comes back in `like`'s dtype -- so that a cast model's concatenations and convolutions see one dtype.
-    Gradients flow back through the casts, each in its input's dtype.  Float32 arguments pass untouched."""
+    """The operators without half kernels (DepthFlowProjection, Interpolation, InterpolationCh; FlowProjection where its
+    layer's `native_half_backward` is off -- its forward has no half kernel either way, its backward has one,
+    FlowProjectionLayer.py): float16 / bfloat16 tensors among `args` are widened to float32 on the host, `apply` (the
+    float32 Function) runs, and the result comes back in `like`'s dtype -- so that a cast model's concatenations and
+    convolutions see one dtype.  Gradients flow back through the casts, each in its input's dtype.  Float32 arguments pass
+    untouched."""
     out = apply(*(cast(a, torch.float32) if isinstance(a, torch.Tensor) and a.dtype in LOWP else a for a in args))
     return cast(out, like.dtype) if like.dtype in LOWP else out

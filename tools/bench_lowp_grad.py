@@ -30,7 +30,13 @@ saved tensors and the gradoutput widened, a float32 forward recomputation, two e
 zero-filled image gradient, the warp's whole backward on libmemc_hip_lp_grad.so, four narrowing casts: what
 _FilterInterpolationBlendLpFunction.backward runs per direction) against the one kernel of libmemc_hip_lp_blend_grad.so on
 the tensors as they are (_direction_backward_fused: what FilterInterpolationBlendLayer(fused_half_backward=True) runs).
-In these rows `widened` is the composed route and `native` the one kernel."""
+In these rows `widened` is the composed route and `native` the one kernel.
+
+The `half_proj` group (--only half_proj) is ONE FlowProjection backward as a model cast to bfloat16 / float16 makes it: a
+half flow, the float32 count of the forward, a half gradoutput, a half gradient.  `widened` is the route through
+_common.host_widened (gradoutput cast to float32, my_lib.FlowProjectionLayer_gpu_backward on the float32 flow autograd kept,
+the gradient cast back); `native` is the one call of libmemc_hip_lp_proj_grad.so on the tensors as they are
+(_FlowProjectionLpFunction.backward).  Casts and allocations are included on both sides."""
 import argparse
 import json
 import math
@@ -74,6 +80,25 @@ def _sets(shape, n, blend, T, half_flow, seed, mixed=False):
             o = torch.rand(B, 1, H, W, device="cuda", generator=g)
             s.update(x2=u["x"].to(T), flow2=u["flow"].to(ft), filt2=u["filt"].to(T), occ0=o.to(T), occ1=(1 - o).to(T))
         out.append(s)
+    return out
+
+
+def _proj_sets(shape, n, T, seed):
+    """flow (T), flow32 (what the widened route's autograd keeps), count (the float32 forward's, fillhole = 0), gout (T)"""
+    import my_package._ext.my_lib as my_lib
+    B, _, H, W = shape
+    out = []
+    for i in range(n):
+        flow = synth.torch_inputs("cuda", B, 1, H, W, flow_kind="smooth", seed=seed + 97 * i)["flow"].to(T)
+        g = torch.Generator("cuda").manual_seed(seed + i)
+        flow32 = flow.float()
+        count, fwd = flow32.new_empty((B, 1, H, W)), torch.empty_like(flow32)
+        ws = my_lib.flow_projection_workspace(flow32, 0)
+        assert my_lib.FlowProjectionLayer_gpu_forward_ws(flow32, count, fwd, 0, ws) == 0
+        out.append({"flow": flow, "flow32": flow32, "count": count,
+                    "gout": torch.randn(B, 2, H, W, device="cuda", generator=g).to(T)})
+        del fwd, ws
+    torch.cuda.synchronize()
     return out
 
 
@@ -126,6 +151,22 @@ def _callers(op, sets, want1):
             grads = BL._direction_backward_fused(s["x"], s["flow"], s["filt"], s["occ"], s["gout"])
             assert grads is not None, "not covered"
             return grads
+    elif op == "proj":
+        import my_package._ext.my_lib as my_lib
+        import my_package._ext.my_lib_lp_proj_grad as my_lib_lp_proj_grad
+
+        def widened():                                       # host_widened's backward
+            s = pick()
+            gout = s["gout"].float()
+            gin = torch.empty_like(s["flow32"])
+            assert my_lib.FlowProjectionLayer_gpu_backward(s["flow32"], s["count"], gout, gin) == 0
+            return gin.to(s["flow"].dtype)
+
+        def native():
+            s = pick()
+            gin = torch.empty_like(s["flow"])
+            assert my_lib_lp_proj_grad.FlowProjectionLayer_gpu_backward_lp(s["flow"], s["count"], s["gout"], gin) == 0, "not covered"
+            return gin
     elif op == "lpblend":
         def widened():                                       # the composed route of one direction: the layer's default
             s = pick()
@@ -164,8 +205,10 @@ def run_case(name, op, shape, T, half_flow, want1, rounds, iters):
         per_set = B * H * W * (2 * C * 4 + 16 * 2 + 2 * 4 + 2)
     if op == "lpblend":
         per_set = B * H * W * (2 * C * 2 + 16 * 2 + 2 * 4 + 2)
+    if op == "proj":
+        per_set = B * H * W * (2 * 2 + 2 * 4 + 4 + 2 * 2)       # half flow, float32 flow, count, half gradoutput
     n = max(2, math.ceil(ROTATE_BYTES / per_set))
-    sets = _sets(shape, n, "one" if op in ("mxblend", "lpblend") else op == "blend", T, half_flow, seed=2468,
+    sets = _proj_sets(shape, n, T, seed=2468) if op == "proj" else _sets(shape, n, "one" if op in ("mxblend", "lpblend") else op == "blend", T, half_flow, seed=2468,
                  mixed=op in ("mx", "mxblend"))
     calls = _callers(op, sets, want1)
     times = {"widened": [], "native": []}
@@ -228,6 +271,11 @@ def main():
                 cases.append(("half_blend_bwd %s %s %s flow" % (tname, "x".join(map(str, shape)),
                                                                 "T" if half_flow else "fp32"),
                               "lpblend", shape, T, half_flow, False))
+    # the half projection group: one FlowProjection backward of a cast model; host_widened's route against
+    # libmemc_hip_lp_proj_grad.so
+    for shape in ((32, 2, 720, 1280), (8, 2, 256, 448)):
+        for tname, T in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
+            cases.append(("half_proj_bwd %s %s" % (tname, "x".join(map(str, shape))), "proj", shape, T, True, False))
     rows = []
     for name, op, shape, T, half_flow, want1 in cases:
         if a.only and a.only not in name:
