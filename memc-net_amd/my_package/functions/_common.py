@@ -69,11 +69,13 @@ def flow_dtype(flow, payload):
 
 
 def host_widened(apply, like, *args):
-    """The operators without half kernels (DepthFlowProjection, Interpolation, InterpolationCh; FlowProjection where its
-    layer's `native_half_backward` is off -- its forward has no half kernel either way, its backward has one,
-    FlowProjectionLayer.py): float16 / bfloat16 tensors among `args` are widened to float32 on the host, `apply` (the
-    float32 Function) runs, and the result comes back in `like`'s dtype -- so that a cast model's concatenations and
-    convolutions see one dtype.  Gradients flow back through the casts, each in its input's dtype.  Float32 arguments pass
+    """The operators and calls without half kernels: the FlowProjection and DepthFlowProjection forwards, the
+    DepthFlowProjection backward, FlowProjection where its layer's `native_half_backward` is off (its backward has a half
+    kernel, FlowProjectionLayer.py), Interpolation / InterpolationCh where their layers' `native_half` is off or the image is
+    float32 beside a half flow (a half image has half kernels, InterpolationLayer.py; a backward they do not cover widens the
+    saved tensors by itself, not through here): float16 / bfloat16 tensors among `args` are widened to float32 on the host,
+    `apply` (the float32 Function) runs, and the result comes back in `like`'s dtype -- so that a cast model's concatenations
+    and convolutions see one dtype.  Gradients flow back through the casts, each in its input's dtype.  Float32 arguments pass
     untouched."""
     out = apply(*(cast(a, torch.float32) if isinstance(a, torch.Tensor) and a.dtype in LOWP else a for a in args))
     return cast(out, like.dtype) if like.dtype in LOWP else out

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """tools/bench_lowp.py -- fp32 / fp16 / bf16 adaptive warps side by side, in one process.
 
-    python tools/bench_lowp.py [--rounds 3] [--iters 10] [--json out.json] [--only lowp|mixed]
+    python tools/bench_lowp.py [--rounds 3] [--iters 10] [--json out.json] [--only lowp|mixed|bilinear]
 
 Cases: FilterInterpolation forward 32x3x720x1280 (smooth flow; fp32 flow and half flow), the fused dual warp + occlusion
 blend 32x3x720x1280, and FilterInterpolation forward 8x64x720x1280 (the context warp).  Each case times fp32 (libmemc_hip.so),
@@ -16,7 +16,15 @@ IT, allocations included: `mixed` (libmemc_hip_mx.so on the tensors as they are)
 taps, occlusions and half flows, then libmemc_hip.so: the layers' route before that library existed), and for the blend
 `fp32` (libmemc_hip.so on fp32 inputs, for orientation).  The arms run in ALTERNATING windows of 8 timed launches (bursts of
 10 for the small shape), six windows each; per row the median of the window medians, the spread (largest minus smallest
-window median) and the bytes per site the route moves."""
+window median) and the bytes per site the route moves.
+
+Bilinear rows (--only bilinear; not part of a run without --only): the forward of InterpolationLayer / InterpolationChLayer for
+a model cast to fp16 / bf16, AS THE LAYER RUNS IT, casts and allocations included: `widened` (_common.host_widened: the image
+and a half flow cast to float32, libmemc_hip.so, the output cast back -- the layers' only route before libmemc_hip_lp_bl.so)
+against `native` (libmemc_hip_lp_bl.so on the tensors as they are), at 32x3x720x1280, 8x3x256x448 and 8x64x720x1280, both
+dtypes, both flow storages.  The two alternate in windows (--rounds of them, at least seven; bursts of 10 launches for the
+small shape), a device synchronise inside each; per group the median of the window medians, the spread of either side
+(largest minus smallest window median over the median) and the ratio native / widened."""
 import argparse
 import json
 import math
@@ -203,9 +211,88 @@ def run_mixed(shape, windows=6, iters=8):
     return rows
 
 
+# ---- the bilinear warp of a cast model: host_widened against libmemc_hip_lp_bl.so -----------------------------------------
+def bilinear_bytes_per_site(route, C, half_flow):
+    """bytes a route moves per site, from the layouts: (casts, kernel)"""
+    f = 2 if half_flow else 4
+    if route == "native":
+        return 0, 2 * C + 2 * f + 2 * C
+    casts = C * (2 + 4) + (2 * (2 + 4) if half_flow else 0) + C * (4 + 2)      # image and half flow widened, output narrowed
+    return casts, 4 * C + 8 + 4 * C
+
+
+def _bilinear_arm(route, C, sets):
+    import my_package._ext.my_lib as my_lib
+    import my_package._ext.my_lib_lp_bl as my_lib_lp_bl
+    which = "InterpolationLayer_gpu_forward" if C == 3 else "InterpolationChLayer_gpu_forward"
+    f32, lp = getattr(my_lib, which), getattr(my_lib_lp_bl, which + "_lp")
+    state = {"i": 0}
+
+    def call():
+        i = state["i"]
+        state["i"] = (i + 1) % len(sets)
+        x, flow = sets[i]
+        if route == "native":
+            out = torch.empty_like(x)
+            err = lp(x, flow, out)
+        else:                                                # host_widened: the casts are per-call allocations and passes
+            x32, flow32 = x.float(), flow.float()
+            wide = torch.empty_like(x32)
+            err = f32(x32, flow32, wide)
+            out = wide.to(x.dtype)
+        if err != 0:
+            raise RuntimeError("bilinear %s returned %d" % (route, err))
+        return out
+
+    return call
+
+
+def run_bilinear(shape, rounds, iters):
+    B, C, H, W = shape
+    sites = B * H * W
+    burst = 10 if sites < (1 << 21) else 1
+    n = max(2, math.ceil(ROTATE_BYTES / (sites * (2 * C + 4))))
+    rows = []
+    for tname, dt in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
+        for half_flow in (False, True):
+            ft = dt if half_flow else torch.float32
+            sets = []
+            for i in range(n):
+                g = torch.Generator("cuda").manual_seed(9753 + i)
+                flow = synth.torch_inputs("cuda", B, 1, H, W, flow_kind="smooth", seed=9753 + 97 * i)["flow"].to(ft)
+                sets.append((torch.rand(B, C, H, W, device="cuda", generator=g).to(dt), flow))
+            calls = {r: _bilinear_arm(r, C, sets) for r in ("widened", "native")}
+            meds = {r: [] for r in calls}
+            for _ in range(max(rounds, 7)):
+                for r in ("widened", "native"):
+                    med, _mn = time_launches(calls[r], warmup=2, iters=iters, burst=burst)
+                    meds[r].append(med)
+            group = {}
+            for r in ("widened", "native"):
+                casts, kern = bilinear_bytes_per_site(r, C, half_flow)
+                t = statistics.median(meds[r])
+                group[r] = {"case": "bilinear_fwd %dx%dx%dx%d" % shape, "dtype": tname, "flow": str(ft).replace("torch.", ""),
+                            "route": r, "us": round(t * 1e6, 1), "windows_us": [round(m * 1e6, 1) for m in meds[r]],
+                            "spread": round((max(meds[r]) - min(meds[r])) / t, 4), "bytes_per_site": casts + kern,
+                            "cast_bytes_per_site": casts, "TBps_moved": round((casts + kern) * sites / t / 1e12, 3),
+                            "input_sets": n, "burst": burst}
+                rows.append(group[r])
+            w, nv = group["widened"], group["native"]
+            nv["ratio"] = round(nv["us"] / w["us"], 3)
+            print("%-30s %-4s flow %-8s widened %9.1f us (spread %5.1f%%, %3d B/site)  native %9.1f us (spread %5.1f%%, %3d B/site)"
+                  "  x%.3f" % (w["case"], tname, w["flow"], w["us"], 100 * w["spread"], w["bytes_per_site"], nv["us"],
+                               100 * nv["spread"], nv["bytes_per_site"], nv["ratio"]))
+            print("    per window  widened %s" % w["windows_us"])
+            print("                native  %s" % nv["windows_us"], flush=True)
+            del sets, calls
+            torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=("lowp", "mixed"), default=None, help="the half rows or the mixed rows alone")
+    ap.add_argument("--only", choices=("lowp", "mixed", "bilinear"), default=None,
+                    help="the half rows, the mixed rows or the bilinear rows alone")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--json", default=None)
@@ -215,13 +302,17 @@ def main():
              ("blend 32x3x720x1280", "blend", (32, 3, 720, 1280), False),
              ("fi_fwd 8x64x720x1280", "fi", (8, 64, 720, 1280), False)]
     rows = []
+    if a.only == "bilinear":
+        for shape in ((32, 3, 720, 1280), (8, 3, 256, 448), (8, 64, 720, 1280)):
+            rows += run_bilinear(shape, a.rounds, a.iters)
+        cases = []
     for name, op, shape, half_flow in ([] if a.only == "mixed" else cases):
         for r in run_case(name, op, shape, half_flow, a.rounds, a.iters):
             rows.append(r)
             print("%-32s %-5s flow %-8s %9.1f us  %3d B/site  %6.3f TB/s  %.3f of 8 TB/s  x%.3f vs fp32" % (
                 r["case"], r["dtype"], r["flow"], r["us"], r["bytes_per_site"], r["TBps"], r["frac_8TBps"],
                 r["ratio_to_fp32"]), flush=True)
-    if a.only != "lowp":
+    if a.only in (None, "mixed"):
         for shape in ((8, 3, 256, 448), (32, 3, 720, 1280)):
             rows += run_mixed(shape)
     if a.json:

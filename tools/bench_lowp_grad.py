@@ -36,7 +36,16 @@ The `half_proj` group (--only half_proj) is ONE FlowProjection backward as a mod
 half flow, the float32 count of the forward, a half gradoutput, a half gradient.  `widened` is the route through
 _common.host_widened (gradoutput cast to float32, my_lib.FlowProjectionLayer_gpu_backward on the float32 flow autograd kept,
 the gradient cast back); `native` is the one call of libmemc_hip_lp_proj_grad.so on the tensors as they are
-(_FlowProjectionLpFunction.backward).  Casts and allocations are included on both sides."""
+(_FlowProjectionLpFunction.backward).  Casts and allocations are included on both sides.
+
+The `half_bilinear` group (--only half_bilinear) is ONE RGB Interpolation backward as a model cast to bfloat16 / float16
+makes it: a half image and gradoutput, the flow in float32 or that dtype.  `widened` is the route through
+_common.host_widened (gradoutput cast to float32, a zero-filled float32 image gradient, my_lib.InterpolationLayer_gpu_backward
+on the float32 image and flow autograd kept, both gradients cast back); `native` is the one call of libmemc_hip_lp_bl.so on
+the tensors as they are (_InterpolationLpFunction.backward: a zero-filled float32 image gradient cast afterwards, the flow
+gradient in the flow's dtype).  Casts and allocations are included on both sides.  Below 2^21 sites a backward is a few tens
+of microseconds in four or five launches, and one backward between two events measures the host's enqueue as much as the
+GPU (tools/bench_ops.time_launches): this group times bursts of 10 there, as tools/bench_lowp.py does for its small shape."""
 import argparse
 import json
 import math
@@ -98,6 +107,21 @@ def _proj_sets(shape, n, T, seed):
         out.append({"flow": flow, "flow32": flow32, "count": count,
                     "gout": torch.randn(B, 2, H, W, device="cuda", generator=g).to(T)})
         del fwd, ws
+    torch.cuda.synchronize()
+    return out
+
+
+def _bilinear_sets(shape, n, T, half_flow, seed):
+    """x, flow, gout as the network holds them; x32, flow32: what the widened route's autograd keeps"""
+    B, C, H, W = shape
+    ft = T if half_flow else torch.float32
+    out = []
+    for i in range(n):
+        g = torch.Generator("cuda").manual_seed(seed + i)
+        flow = synth.torch_inputs("cuda", B, 1, H, W, flow_kind="smooth", seed=seed + 97 * i)["flow"].to(ft)
+        x = torch.rand(B, C, H, W, device="cuda", generator=g).to(T)
+        out.append({"x": x, "flow": flow, "x32": x.float(), "flow32": flow.float(),
+                    "gout": torch.randn(B, C, H, W, device="cuda", generator=g).to(T)})
     torch.cuda.synchronize()
     return out
 
@@ -167,6 +191,22 @@ def _callers(op, sets, want1):
             gin = torch.empty_like(s["flow"])
             assert my_lib_lp_proj_grad.FlowProjectionLayer_gpu_backward_lp(s["flow"], s["count"], s["gout"], gin) == 0, "not covered"
             return gin
+    elif op == "bl":
+        import my_package._ext.my_lib as my_lib
+        import my_package._ext.my_lib_lp_bl as my_lib_lp_bl
+
+        def widened():                                       # host_widened's backward
+            s = pick()
+            gout = s["gout"].float()
+            g1, g2 = torch.zeros_like(s["x32"]), torch.empty_like(s["flow32"])
+            assert my_lib.InterpolationLayer_gpu_backward(s["x32"], s["flow32"], gout, g1, g2) == 0
+            return g1.to(s["x"].dtype), g2.to(s["flow"].dtype)
+
+        def native():
+            s = pick()
+            g1, g2 = torch.zeros_like(s["x"], dtype=torch.float32), torch.empty_like(s["flow"])
+            assert my_lib_lp_bl.InterpolationLayer_gpu_backward_lp(s["x"], s["flow"], s["gout"], g1, g2) == 0, "not covered"
+            return g1.to(s["x"].dtype), g2
     elif op == "lpblend":
         def widened():                                       # the composed route of one direction: the layer's default
             s = pick()
@@ -207,16 +247,19 @@ def run_case(name, op, shape, T, half_flow, want1, rounds, iters):
         per_set = B * H * W * (2 * C * 2 + 16 * 2 + 2 * 4 + 2)
     if op == "proj":
         per_set = B * H * W * (2 * 2 + 2 * 4 + 4 + 2 * 2)       # half flow, float32 flow, count, half gradoutput
+    if op == "bl":
+        per_set = B * H * W * (2 * C * (2 + 4) + 2 * 4)         # half image and gradoutput, their float32 copies, the flow
     n = max(2, math.ceil(ROTATE_BYTES / per_set))
-    sets = _proj_sets(shape, n, T, seed=2468) if op == "proj" else _sets(shape, n, "one" if op in ("mxblend", "lpblend") else op == "blend", T, half_flow, seed=2468,
+    sets = _proj_sets(shape, n, T, seed=2468) if op == "proj" else _bilinear_sets(shape, n, T, half_flow, seed=2468) if op == "bl" else _sets(shape, n, "one" if op in ("mxblend", "lpblend") else op == "blend", T, half_flow, seed=2468,
                  mixed=op in ("mx", "mxblend"))
     calls = _callers(op, sets, want1)
+    burst = 10 if op == "bl" and B * H * W < (1 << 21) else 1
     times = {"widened": [], "native": []}
     for _ in range(rounds):
         for route in ("widened", "native"):
-            med, _mn = time_launches(calls[route], warmup=2, iters=iters)
+            med, _mn = time_launches(calls[route], warmup=2, iters=iters, burst=burst)
             times[route].append(med)
-    row = {"case": name, "rounds": rounds, "iters": iters, "input_sets": n}
+    row = {"case": name, "rounds": rounds, "iters": iters, "input_sets": n, "burst": burst}
     for route in ("widened", "native"):
         ts = times[route]
         m = statistics.median(ts)
@@ -276,6 +319,14 @@ def main():
     for shape in ((32, 2, 720, 1280), (8, 2, 256, 448)):
         for tname, T in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
             cases.append(("half_proj_bwd %s %s" % (tname, "x".join(map(str, shape))), "proj", shape, T, True, False))
+    # the half bilinear group: one RGB Interpolation backward of a cast model; host_widened's route against
+    # libmemc_hip_lp_bl.so
+    for shape in (big, (8, 3, 256, 448)):
+        for tname, T in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
+            for half_flow in (False, True):
+                cases.append(("half_bilinear_bwd %s %s %s flow" % (tname, "x".join(map(str, shape)),
+                                                                   "T" if half_flow else "fp32"),
+                              "bl", shape, T, half_flow, True))
     rows = []
     for name, op, shape, T, half_flow, want1 in cases:
         if a.only and a.only not in name:
