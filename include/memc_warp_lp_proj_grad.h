@@ -21,8 +21,8 @@
  *
  * Coverage (return 1 outside it): a width that is a multiple of four from 8 on; input1, gradoutput and gradinput1 with
  * row / channel / batch strides that are multiples of four elements and 8-byte aligned bases; a dword-aligned count; every
- * plane within 32-bit byte offsets.  There is no half kernel for other calls (nor for DepthFlowProjection): the caller
- * widens and takes FlowProjectionLayer_gpu_backward.
+ * plane within 32-bit byte offsets.  There is no half kernel for other calls: the caller widens and takes
+ * FlowProjectionLayer_gpu_backward.  (DepthFlowProjection has a library of its own: memc_warp_lp_dproj_grad.h.)
  *
  * Layout: NCHW, element strides (int64), w-stride 1; input1 [B, 2, H, W], count [B, 1, H, W]; gradoutput and gradinput1
  * have input1's shape and layout.

@@ -69,9 +69,10 @@ def flow_dtype(flow, payload):
 
 
 def host_widened(apply, like, *args):
-    """The operators and calls without half kernels: the FlowProjection and DepthFlowProjection forwards, the
-    DepthFlowProjection backward, FlowProjection where its layer's `native_half_backward` is off (its backward has a half
-    kernel, FlowProjectionLayer.py), Interpolation / InterpolationCh where their layers' `native_half` is off or the image is
+    """The operators and calls without half kernels: the FlowProjection and DepthFlowProjection forwards, FlowProjection and
+    DepthFlowProjection where their layers' `native_half_backward` is off (their backward passes have half kernels,
+    FlowProjectionLayer.py and DepthFlowProjectionLayer.py), DepthFlowProjection with a float32 tensor beside a half one,
+    Interpolation / InterpolationCh where their layers' `native_half` is off or the image is
     float32 beside a half flow (a half image has half kernels, InterpolationLayer.py; a backward they do not cover widens the
     saved tensors by itself, not through here): float16 / bfloat16 tensors among `args` are widened to float32 on the host,
     `apply` (the float32 Function) runs, and the result comes back in `like`'s dtype -- so that a cast model's concatenations

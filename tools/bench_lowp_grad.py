@@ -38,6 +38,13 @@ _common.host_widened (gradoutput cast to float32, my_lib.FlowProjectionLayer_gpu
 the gradient cast back); `native` is the one call of libmemc_hip_lp_proj_grad.so on the tensors as they are
 (_FlowProjectionLpFunction.backward).  Casts and allocations are included on both sides.
 
+The `half_dproj` group (--only half_dproj) is ONE DepthFlowProjection backward as a model cast to bfloat16 / float16 makes
+it: a half flow and depth, the float32 count and output of the forward, a half gradoutput, two half gradients.  `widened`
+is the route through _common.host_widened, what DepthFlowProjectionLayer.native_half_backward = False runs (gradoutput cast
+to float32, my_lib.DepthFlowProjectionLayer_gpu_backward on the float32 flow and depth autograd kept, both gradients cast
+back); `native` is the one call of libmemc_hip_lp_dproj_grad.so on the tensors as they are
+(_DepthFlowProjectionLpFunction.backward).  Casts and allocations are included on both sides.
+
 The `half_bilinear` group (--only half_bilinear) is ONE RGB Interpolation backward as a model cast to bfloat16 / float16
 makes it: a half image and gradoutput, the flow in float32 or that dtype.  `widened` is the route through
 _common.host_widened (gradoutput cast to float32, a zero-filled float32 image gradient, my_lib.InterpolationLayer_gpu_backward
@@ -107,6 +114,27 @@ def _proj_sets(shape, n, T, seed):
         out.append({"flow": flow, "flow32": flow32, "count": count,
                     "gout": torch.randn(B, 2, H, W, device="cuda", generator=g).to(T)})
         del fwd, ws
+    torch.cuda.synchronize()
+    return out
+
+
+def _dproj_sets(shape, n, T, seed):
+    """flow, depth (T), flow32, depth32 (what the widened route's autograd keeps), count and out (the float32 forward's,
+    fillhole = 0), gout (T)"""
+    import my_package._ext.my_lib as my_lib
+    B, _, H, W = shape
+    out = []
+    for i in range(n):
+        flow = synth.torch_inputs("cuda", B, 1, H, W, flow_kind="smooth", seed=seed + 97 * i)["flow"].to(T)
+        g = torch.Generator("cuda").manual_seed(seed + i)
+        depth = (0.1 + torch.rand(B, 1, H, W, device="cuda", generator=g)).to(T)
+        flow32, depth32 = flow.float(), depth.float()
+        count, fwd = flow32.new_empty((B, 1, H, W)), torch.empty_like(flow32)
+        ws = my_lib.flow_projection_workspace(flow32, 0, depth=True)
+        assert my_lib.DepthFlowProjectionLayer_gpu_forward_ws(flow32, depth32, count, fwd, 0, ws) == 0
+        out.append({"flow": flow, "depth": depth, "flow32": flow32, "depth32": depth32, "count": count, "out": fwd,
+                    "gout": torch.randn(B, 2, H, W, device="cuda", generator=g).to(T)})
+        del ws
     torch.cuda.synchronize()
     return out
 
@@ -191,6 +219,23 @@ def _callers(op, sets, want1):
             gin = torch.empty_like(s["flow"])
             assert my_lib_lp_proj_grad.FlowProjectionLayer_gpu_backward_lp(s["flow"], s["count"], s["gout"], gin) == 0, "not covered"
             return gin
+    elif op == "dproj":
+        import my_package._ext.my_lib as my_lib
+        import my_package._ext.my_lib_lp_dproj_grad as my_lib_lp_dproj_grad
+
+        def widened():                                       # host_widened's backward
+            s = pick()
+            gout = s["gout"].float()
+            g1, g2 = torch.empty_like(s["flow32"]), torch.empty_like(s["depth32"])
+            assert my_lib.DepthFlowProjectionLayer_gpu_backward(s["flow32"], s["depth32"], s["count"], s["out"], gout, g1, g2) == 0
+            return g1.to(s["flow"].dtype), g2.to(s["depth"].dtype)
+
+        def native():
+            s = pick()
+            g1, g2 = torch.empty_like(s["flow"]), torch.empty_like(s["depth"])
+            assert my_lib_lp_dproj_grad.DepthFlowProjectionLayer_gpu_backward_lp(
+                s["flow"], s["depth"], s["count"], s["out"], s["gout"], g1, g2) == 0, "not covered"
+            return g1, g2
     elif op == "bl":
         import my_package._ext.my_lib as my_lib
         import my_package._ext.my_lib_lp_bl as my_lib_lp_bl
@@ -247,10 +292,12 @@ def run_case(name, op, shape, T, half_flow, want1, rounds, iters):
         per_set = B * H * W * (2 * C * 2 + 16 * 2 + 2 * 4 + 2)
     if op == "proj":
         per_set = B * H * W * (2 * 2 + 2 * 4 + 4 + 2 * 2)       # half flow, float32 flow, count, half gradoutput
+    if op == "dproj":
+        per_set = B * H * W * (3 * 2 + 3 * 4 + 4 + 2 * 4 + 2 * 2)   # half flow and depth, their float32 copies, count, output, half gradoutput
     if op == "bl":
         per_set = B * H * W * (2 * C * (2 + 4) + 2 * 4)         # half image and gradoutput, their float32 copies, the flow
     n = max(2, math.ceil(ROTATE_BYTES / per_set))
-    sets = _proj_sets(shape, n, T, seed=2468) if op == "proj" else _bilinear_sets(shape, n, T, half_flow, seed=2468) if op == "bl" else _sets(shape, n, "one" if op in ("mxblend", "lpblend") else op == "blend", T, half_flow, seed=2468,
+    sets = _proj_sets(shape, n, T, seed=2468) if op == "proj" else _dproj_sets(shape, n, T, seed=2468) if op == "dproj" else _bilinear_sets(shape, n, T, half_flow, seed=2468) if op == "bl" else _sets(shape, n, "one" if op in ("mxblend", "lpblend") else op == "blend", T, half_flow, seed=2468,
                  mixed=op in ("mx", "mxblend"))
     calls = _callers(op, sets, want1)
     burst = 10 if op == "bl" and B * H * W < (1 << 21) else 1
@@ -319,6 +366,11 @@ def main():
     for shape in ((32, 2, 720, 1280), (8, 2, 256, 448)):
         for tname, T in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
             cases.append(("half_proj_bwd %s %s" % (tname, "x".join(map(str, shape))), "proj", shape, T, True, False))
+    # the half depth projection group: one DepthFlowProjection backward of a cast model; host_widened's route (the layer
+    # with native_half_backward off) against libmemc_hip_lp_dproj_grad.so
+    for shape in ((32, 2, 720, 1280), (8, 2, 256, 448)):
+        for tname, T in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
+            cases.append(("half_dproj_bwd %s %s" % (tname, "x".join(map(str, shape))), "dproj", shape, T, True, False))
     # the half bilinear group: one RGB Interpolation backward of a cast model; host_widened's route against
     # libmemc_hip_lp_bl.so
     for shape in (big, (8, 3, 256, 448)):
