@@ -1,7 +1,8 @@
-// memc_fi_abi.hpp -- what the C ABIs of the seven satellite warp libraries share (host code only): lp_filter_interpolation.hip
+// memc_fi_abi.hpp -- what the C ABIs of the eight satellite warp libraries share (host code only): lp_filter_interpolation.hip
 // (memc_warp_lp.h), lp_fi_bwd_c3.hip (memc_warp_lp_grad.h), fi_blend_bwd_c3.hip (memc_warp_blend_grad.h),
 // mx_filter_interpolation.hip (memc_warp_mx.h), mx_fi_bwd_c3.hip (memc_warp_mx_grad.h), mx_fi_blend_bwd_c3.hip
-// (memc_warp_mx_blend_grad.h) and lp_fi_blend_bwd_c3.hip (memc_warp_lp_blend_grad.h).  The filter-side rules, the
+// (memc_warp_mx_blend_grad.h), lp_fi_blend_bwd_c3.hip (memc_warp_lp_blend_grad.h) and fi_stack.hip (memc_warp_stack.h: the
+// filter-side rule, the sizes, the tile grid and the return codes).  The filter-side rules, the
 // coverage predicates, the three check sequences that more than one entry point runs, the tile grid, the call descriptors
 // filled from the tensors, the launch of the tiled backward kernels, the backward's PART choice and the dtype dispatch.  An
 // entry point keeps its dtype check, its filter-side rule, its coverage test and its path strings; the order of every
