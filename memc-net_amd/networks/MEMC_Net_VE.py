@@ -21,7 +21,8 @@ Differences, deliberate:
   * `align_corners` of the bilinear upsamplings is a constructor argument, as on the other classes (networks/_base.py);
   * `fused_stack`: the rectifier input is allocated once and filled by two stacked warps
     (my_package.modules.FilterInterpolationStackModule, an extension of this repository's my_package) instead of twelve
-    FilterInterpolationModule calls and torch.cat.  Same values bit for bit (tests/test_gpu_stack.py).
+    FilterInterpolationModule calls and torch.cat.  Same values bit for bit (tests/test_gpu_stack.py; a model cast to
+    float16 / bfloat16: tests/test_gpu_lp_stack.py).
 """
 import warnings
 
@@ -57,8 +58,9 @@ class MEMC_Net_VE(nn.Module):
         # the rectifier input filled by two stacked warps instead of twelve warps and torch.cat: measured x0.37 / x0.39 of
         # the composed route's time (314 against 845 us, 904 against 2305 us: 1 / 4 septuplets of 320 x 512,
         # profiles/r24_ve_stack.txt), faster in both groups, so on by default; a whole inference step x0.97 (21.3 against
-        # 21.9 ms): the dense layers dominate.  float32 on the GPU only; anything else takes the composed route whatever
-        # this says
+        # 21.9 ms): the dense layers dominate.  On the GPU, for float32 and for a model cast to float16 / bfloat16
+        # (FilterInterpolationStackLayer.native_half has that route's numbers); autocast and mixed dtypes take the composed
+        # route whatever this says
         self.fused_stack = True
         fs2 = filter_size * filter_size
         self.ctx_ch = 64
@@ -103,9 +105,13 @@ class MEMC_Net_VE(nn.Module):
         return self._flow(pairs), run_unet(self.initScaleNets_filter1, run_unet(self.initScaleNets_filter, pairs))
 
     def _use_stack(self, inputs, flow, taps):
+        # one dtype throughout -- float32, or float16 / bfloat16 for a cast model -- and no autocast (under it torch.cat
+        # promotes the rectifier input to float32 while the warps stay half: the composed route's business)
+        dtype = flow.dtype
         return (self.fused_stack and FilterInterpolationStackModule is not None and not torch.is_autocast_enabled()
-                and all(t.is_cuda and t.dtype == torch.float32 for t in tuple(inputs) + (flow, taps))
-                and self.ctxNet.conv1.weight.dtype == torch.float32)
+                and dtype in (torch.float32, torch.float16, torch.bfloat16)
+                and all(t.is_cuda and t.dtype == dtype for t in tuple(inputs) + (flow, taps))
+                and self.ctxNet.conv1.weight.dtype == dtype)
 
     def _rectifier_input_composed(self, inputs, flow, taps, contexts=None):
         """twelve warps and torch.cat: the reference's sequence (:205-256; tests/golden/ve_call_trace.json)"""

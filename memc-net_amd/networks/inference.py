@@ -41,11 +41,13 @@ def check_precision(dtype, autocast):
 
 
 def run_model(model, x, autocast=None):
-    """model(x) without gradients, inside torch.autocast(dtype=autocast) where that is asked for"""
+    """model(x) without gradients, inside torch.autocast(dtype=autocast) where that is asked for; x: a tensor, or a list of
+    tensors on one device (MEMC_Net_VE's seven frames)"""
     with torch.no_grad():
         if autocast is None:
             return model(x)
-        with torch.autocast(x.device.type, dtype=autocast):
+        first = x[0] if isinstance(x, (list, tuple)) else x
+        with torch.autocast(first.device.type, dtype=autocast):
             return model(x)
 
 

@@ -54,28 +54,31 @@ def _read_septuplet(input_dir, target_dir, clip):
     return frames, gt
 
 
-def _enhance_host(model, frames, device):
-    """the enhanced centre frame as uint8 [h, w, 3], the pixel work in numpy and torch on the host's side of the model"""
+def _enhance_host(model, frames, device, half=None, autocast=None):
+    """the enhanced centre frame as uint8 [h, w, 3], the pixel work in numpy and torch on the host's side of the model; `half`:
+    the frames are cast to it and padded in it (a cast model); a half result is widened before it is rounded (exact)"""
     import torch
     import torch.nn.functional as F
-    from .inference import pad_amounts
+    from .inference import pad_amounts, run_model
     h, w, _c = frames[0].shape
     left, right, top, bottom = pad_amounts(h, w)
     xs = [torch.from_numpy(np.transpose(img, (2, 0, 1))[None].astype(np.float32) / 255.0).to(device) for img in frames]
+    if half is not None:
+        xs = [x.to(half) for x in xs]
     xs = [F.pad(x, (left, right, top, bottom), mode="replicate") for x in xs]
-    with torch.no_grad():
-        y = model(xs)
+    y = run_model(model, xs, autocast)
     y = (y[0] if isinstance(y, (tuple, list)) else y)[0, :, top:top + h, left:left + w]
     return np.ascontiguousarray(np.transpose(np.round(255.0 * y.float().clamp(0.0, 1.0).cpu().numpy()), (1, 2, 0)).astype(np.uint8))
 
 
-def _enhance_gpu(model, frames, gt, device, ssim):
+def _enhance_gpu(model, frames, gt, device, ssim, half=None, autocast=None):
     """the same with the pixel work on the device (my_package._ext.my_lib_still, include/memc_still.h): the raw bytes of the
     seven frames and the target go up, decode writes the padded network inputs, the quantised crop of the result is scored;
-    the result's bytes and the integer sums (and the three channels' SSIM) come down.  -> (uint8 [h, w, 3], scores)"""
+    the result's bytes and the integer sums (and the three channels' SSIM) come down.  `half`: decode writes the planes in
+    that storage (a cast model); quantise takes the result in whatever dtype the model returns.  -> (uint8 [h, w, 3], scores)"""
     import torch
     import my_package._ext.my_lib_still as S
-    from .inference import pad_amounts
+    from .inference import pad_amounts, run_model
 
     def ok(code, what):
         if code != 0:
@@ -84,10 +87,9 @@ def _enhance_gpu(model, frames, gt, device, ssim):
     h, w, _c = frames[0].shape
     left, right, top, bottom = pads = pad_amounts(h, w)
     raw = torch.from_numpy(np.ascontiguousarray(np.stack(frames + [gt]))).to(device)      # [seven frames | target], uint8
-    x = torch.empty((7, 3, h + top + bottom, w + left + right), dtype=torch.float32, device=device)
+    x = torch.empty((7, 3, h + top + bottom, w + left + right), dtype=torch.float32 if half is None else half, device=device)
     ok(S.rgb8_decode(raw[:7], x, pads), "memc_rgb8_decode")
-    with torch.no_grad():
-        y = model([x[k:k + 1] for k in range(7)])
+    y = run_model(model, [x[k:k + 1] for k in range(7)], autocast)
     y = (y[0] if isinstance(y, (tuple, list)) else y)[:, :, top:top + h, left:left + w]
     rec = torch.empty((1, h, w, 3), dtype=torch.uint8, device=device)
     ok(S.rgb8_quantise(y, rec), "memc_rgb8_quantise")
@@ -105,7 +107,8 @@ def _enhance_gpu(model, frames, gt, device, ssim):
     return rec[0].cpu().numpy(), scores + ((float(np.mean(down[2:].view(np.float64))),) if ssim else ())
 
 
-def enhance_septuplet_tree(model, input_dir, target_dir, out_dir, device, list_file=None, gpu_io=False, ssim=False):
+def enhance_septuplet_tree(model, input_dir, target_dir, out_dir, device, list_file=None, gpu_io=False, ssim=False,
+                           dtype=None, autocast=None):
     """For every clip (list_clips): im1.png .. im7.png of input_dir in, the enhanced centre frame out
     (out_dir/<sequence>/<clip>/im4.png), scored against target_dir/<sequence>/<clip>/im4.png; the averages go to
     out_dir/metrics.txt (metrics_text).  `model`: seven [1, 3, H, W] frames -> the enhanced centre (MEMC_Net_VE at inference;
@@ -113,8 +116,13 @@ def enhance_septuplet_tree(model, input_dir, target_dir, out_dir, device, list_f
     under ssim=True (ValueError for a picture with h or w below 7).
     gpu_io=True (a CUDA device; otherwise ValueError, before a file is read): the float conversion, the padding, the
     quantisation, the error sums and the SSIM run on the device (libmemc_hip_still.so, libmemc_hip_ssim.so) instead of in
-    numpy on the host: the same bytes and the same floats."""
+    numpy on the host: the same bytes and the same floats.
+    dtype / autocast: interpolate_png_tree's (inference.check_precision: a model cast to float16 / bfloat16 is fed planes of
+    `dtype`, or a float32 model runs inside torch.autocast on float32 planes), checked before a file is read; a half result
+    is widened to float32 before it is rounded."""
     import torch
+    from .inference import check_precision
+    half = check_precision(dtype, autocast)
     if gpu_io and torch.device(device).type != "cuda":
         raise ValueError("gpu_io=True needs a CUDA (HIP) device, got %s" % (device,))
     results = []
@@ -123,9 +131,9 @@ def enhance_septuplet_tree(model, input_dir, target_dir, out_dir, device, list_f
         if ssim and min(gt.shape[:2]) < 7:
             raise ValueError("%s: SSIM's 7 x 7 window needs h and w of at least 7, got %dx%d" % (clip, gt.shape[1], gt.shape[0]))
         if gpu_io:
-            rec, scores = _enhance_gpu(model, frames, gt, torch.device(device), ssim)
+            rec, scores = _enhance_gpu(model, frames, gt, torch.device(device), ssim, half, autocast)
         else:
-            rec = _enhance_host(model, frames, device)
+            rec = _enhance_host(model, frames, device, half, autocast)
             scores = rgb_scores(rec, gt)[:2] + ((rgb_ssim(rec, gt),) if ssim else ())
         os.makedirs(os.path.join(out_dir, clip), exist_ok=True)
         write_png(os.path.join(out_dir, clip, CENTRE), rec)

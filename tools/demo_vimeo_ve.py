@@ -6,6 +6,7 @@ target.
     python tools/demo_vimeo_ve.py --input vimeo/input --target vimeo/target --output results
                                   [--list vimeo/sep_testlist.txt] [--weights best.pth --align-corners]
                                   [--gpu-io] [--ssim] [--composed]
+                                  [--precision {fp32,bf16,fp16,autocast-bf16,autocast-fp16}]
 
 Reads <input>/<sequence>/<clip>/im1.png .. im7.png, replicate-pads every frame like demo_Vimeo_VE.py:115-135 (to multiples
 of 128; a side that already is one gets 32 + 32, so 256 x 448 runs as 320 x 512), runs MEMC_Net_VE and crops; results/
@@ -15,8 +16,9 @@ are those --list names (one <sequence>/<clip> per line), or every clip of the tr
 networks/png_io.py (8 bits per sample, non-interlaced).  Without --weights the network runs on its random initialisation
 (plumbing check only).  --gpu-io does the pixel work around the network (float conversion, padding, quantisation, error
 sums, SSIM) on the device: the same bytes and numbers.  --composed fills the rectifier's input by twelve warps and
-torch.cat, the reference's sequence, instead of two stacked warps (MEMC_Net_VE.fused_stack).  Needs a GPU: the operators
-have no CPU path.
+torch.cat, the reference's sequence, instead of two stacked warps (MEMC_Net_VE.fused_stack).  --precision runs the network
+in reduced precision: a cast model (bf16, fp16) or a float32 model under torch.autocast.  Needs a GPU: the operators have
+no CPU path.
 """
 import argparse
 import os
@@ -41,6 +43,10 @@ def main(argv=None):
                     help="frame I/O and scores on the device (libmemc_hip_still.so) instead of in numpy on the host")
     ap.add_argument("--ssim", action="store_true", help="also report the RGB SSIM (mean over the three channels)")
     ap.add_argument("--composed", action="store_true", help="twelve warps and torch.cat instead of two stacked warps")
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "fp16", "autocast-bf16", "autocast-fp16"],
+                    help="fp32 (default): as ever.  bf16 / fp16: the model is cast after its weights are loaded and fed planes of "
+                         "that dtype -- bf16 is the cast mode to prefer, an fp16 cast can overflow in the dense layers.  "
+                         "autocast-bf16 / autocast-fp16: the float32 model runs inside torch.autocast on float32 planes")
     a = ap.parse_args(argv)
 
     import torch
@@ -58,9 +64,15 @@ def main(argv=None):
     if a.composed:
         net.fused_stack = False
     net = net.to(dev).eval()
+    half = {"bf16": torch.bfloat16, "fp16": torch.float16}
+    dtype = half.get(a.precision)
+    autocast = half.get(a.precision[len("autocast-"):]) if a.precision.startswith("autocast-") else None
+    if dtype is not None:
+        net = net.to(dtype)
+    kw = dict(dtype=dtype, autocast=autocast) if a.precision != "fp32" else {}      # a default run makes the call it always made
     os.makedirs(a.output, exist_ok=True)
     results = networks.enhance_septuplet_tree(net, a.input, a.target, a.output, dev, list_file=a.list or None,
-                                              gpu_io=a.gpu_io, ssim=a.ssim)
+                                              gpu_io=a.gpu_io, ssim=a.ssim, **kw)
     what = "interpolation error / PSNR / SSIM" if a.ssim else "interpolation error / PSNR"
     fmt = " / ".join(["%.4f"] * (3 if a.ssim else 2))
     for r in results:
