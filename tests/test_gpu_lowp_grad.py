@@ -4,9 +4,14 @@ autograd Functions.
 Contract: for the same inputs, gradinput2 and gradinput3 equal, bit for bit, the fp32 library's (libmemc_hip.so) results
 on the widened inputs rounded to their dtype -- with the same gradinput1 choice (NULL or a buffer), which picks the same
 summation order for sites that no LDS band covers.  gradinput1 is an fp32 buffer flushed with fp32 atomics on both sides,
-so neither side is bit-reproducible from run to run: after rounding to T it must lie within one ulp_T of the fp32
-library's everywhere and equal it on at least 99.9 % of the elements -- a condition the fp32 library run twice is held to
-first (the control)."""
+so neither side is bit-reproducible from run to run.  Its rule is image_gradients_agree: every finite cell of EITHER side,
+before any rounding to T, lies within tests/_image_grad.py's bound of the float64 restatement of the operation on the call's
+own inputs -- a bound derived from the kernels' sources (the packed planes' grid, fp32's roundings of the terms and of the
+running sums), which holds for every order the hardware may add in and which a dropped or misweighted term of 1e-4 breaks;
+after rounding to T the two sides have the same non-finite pattern and are equal on at least 99.9 % of the elements.  "Within
+one ulp_T of each other", the earlier rule, follows wherever 2 * bound <= ulp_T (85 - 99 % of the cells:
+tests/test_image_grad_bound.py); elsewhere, where terms cancel to a small sum, two correct results may differ by more, and the
+bound replaces it.  The fp32 library run twice is held to the rule first (the control)."""
 import os
 import sys
 
@@ -19,6 +24,7 @@ for _p in (ROOT, os.path.join(ROOT, "memc-net_amd"), os.path.dirname(os.path.abs
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import _image_grad as IG     # noqa: E402
 from tools import synth      # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -81,9 +87,22 @@ def ulp(v, dtype):
     return torch.ldexp(torch.ones_like(v), e - mant)
 
 
-def image_gradients_agree(a, b, T, label):
-    """a, b: fp32 image gradients.  Rounded to T: the same non-finite pattern, within one ulp_T everywhere, equal on at
-    least 99.9 % of the elements."""
+TNAME = {torch.float16: "fp16", torch.bfloat16: "bf16"}
+
+
+def image_reference(flow, taps, gout, fs=4, planes=True):
+    """tests/_image_grad.Reference of one call's inputs (tensors of any storage, widened here): made once per call, shared
+    by the checks of that call.  planes: the kernels pack the image gradient into LDS planes (C == 3, fs == 4)."""
+    return IG.Reference(flow, taps, gout, fs=fs, planes=planes)
+
+
+def image_gradients_agree(a, b, T, label, inputs, stored=(False, False)):
+    """a, b: image gradients of the same call (fp32, or widened from T: then stored[side] is True and the bound gains
+    ulp_T / 2).  inputs: image_reference(...) of the call, or its (flow, taps, gradoutput).
+    Before rounding: every finite cell of a and of b lies within the derived bound of the float64 restatement.  Rounded to T:
+    the same non-finite pattern, equal on at least 99.9 % of the elements.  Cells whose terms are not all finite (an Inf / NaN
+    input reaches them) have no bound: there the finite results stay within one ulp_T of each other."""
+    ref = inputs if isinstance(inputs, IG.Reference) else image_reference(*inputs)
     ra, rb = a.to(T).float(), b.to(T).float()
     assert torch.equal(torch.isnan(ra), torch.isnan(rb)), label
     fin = torch.isfinite(ra) & torch.isfinite(rb)
@@ -91,8 +110,17 @@ def image_gradients_agree(a, b, T, label):
     d = (ra[fin] - rb[fin]).abs()
     tol = ulp(torch.maximum(ra[fin].abs(), rb[fin].abs()), T)
     same = float(((ra == rb) | (torch.isnan(ra) & torch.isnan(rb))).float().mean())
-    print("%s: max diff %.3g ulp_T, equal %.6f" % (label, float((d / tol).max()) if d.numel() else 0.0, same))
-    assert bool((d <= tol).all()), label
+    worst = []
+    for side, st in zip((a, b), stored):
+        r, _ok = ref.ratio(side.detach().float().cpu().numpy(), TNAME[T] if st else None)
+        worst.append(float(r.max()))
+    print("%s: max diff %.3g ulp_T, equal %.6f, max err / bound %.3f and %.3f (bound up to %.3g)"
+          % (label, float((d / tol).max()) if d.numel() else 0.0, same, worst[0], worst[1],
+             float(np.nanmax(np.where(ref.finite, ref.bound(), 0.0)))))
+    assert worst[0] <= 1.0 and worst[1] <= 1.0, (label, worst)
+    loose = torch.from_numpy(~ref.finite).to(fin.device) & fin                   # no bound: today's treatment
+    dl = (ra[loose] - rb[loose]).abs()
+    assert bool((dl <= ulp(torch.maximum(ra[loose].abs(), rb[loose].abs()), T)).all()), label
     assert same >= 0.999, (label, same)
 
 
@@ -120,12 +148,13 @@ def test_image_gradient_matches_the_fp32_library(tname, kind):
     T = DTYPES[tname]
     for i, shape in enumerate(SHAPES):
         x, flow, filt, gout = half_inputs(200 + i, shape, kind, T, False, True)
+        ref = image_reference(flow, filt, gout)
         a1, _, _ = fp32(x, flow, filt, gout, True)
         b1, _, _ = fp32(x, flow, filt, gout, True)
-        image_gradients_agree(a1, b1, T, "control: fp32 twice %s %s" % (kind, shape))
+        image_gradients_agree(a1, b1, T, "control: fp32 twice %s %s" % (kind, shape), ref)
         err, g1, _, _ = native(x, flow, filt, gout, True)
         assert err == 0 and g1.dtype == torch.float32
-        image_gradients_agree(g1, a1, T, "native vs fp32 %s %s" % (kind, shape))
+        image_gradients_agree(g1, a1, T, "native vs fp32 %s %s" % (kind, shape), ref)
 
 
 @pytest.mark.parametrize("tname", sorted(DTYPES))
@@ -183,7 +212,7 @@ def test_aligned_views_are_served_and_shifted_ones_declined(tname):
         if served:
             w1, w2, w3 = fp32(vx, vf, vk, vg, True)
             assert torch.equal(v2, w2) and torch.equal(v3, w3.to(T))
-            image_gradients_agree(v1.contiguous(), w1, T, "view")
+            image_gradients_agree(v1.contiguous(), w1, T, "view", (vf, vk, vg))
         else:                                                 # nothing touched
             assert bool((v1 == 0).all()) and bool(torch.isnan(v2).all()) and bool(torch.isnan(v3).all())
 
@@ -213,7 +242,7 @@ def test_fp16_overflow_and_infinite_gradoutput():
             ok = ~torch.isnan(want)
             assert torch.equal(got[ok], want[ok])
         if with_image:
-            image_gradients_agree(g1, w1, T, "inf gradoutput")
+            image_gradients_agree(g1, w1, T, "inf gradoutput", (flow, filt, inf))
 
 
 def device_inputs(seed, shape, T):
@@ -237,7 +266,7 @@ def test_large_shapes():
         assert torch.equal(g2, w2), shape
         assert torch.equal(g3, w3.to(T)), shape
         if with_image:
-            image_gradients_agree(g1, w1, T, "config 2")
+            image_gradients_agree(g1, w1, T, "config 2", (flow, filt, gout))
         del x, flow, filt, gout, g1, g2, g3, w1, w2, w3
         torch.cuda.empty_cache()
 
@@ -258,7 +287,7 @@ def native_calls(monkeypatch):
 
 
 def _layer_grads(T, shape, fs, image_grad, seed=700):
-    """gradients of the half layer and of the fp32 layer on the widened inputs, rounded"""
+    """gradients of the half layer and of the fp32 layer on the widened inputs, rounded; the inputs (flow, taps, gradoutput) in T"""
     from my_package.modules.FilterInterpolationModule import FilterInterpolationModule
     B, C, H, W = shape
     rng = np.random.default_rng(seed)
@@ -272,7 +301,8 @@ def _layer_grads(T, shape, fs, image_grad, seed=700):
         FilterInterpolationModule()(*ts).backward(gout.to(dt))
         return [t.grad for t in ts]
 
-    return run(T), run(torch.float32)
+    held = tuple(torch.from_numpy(a).cuda().to(T) for a in arrs[1:]) + (gout,)
+    return run(T), run(torch.float32), held
 
 
 @pytest.mark.parametrize("tname", sorted(DTYPES))
@@ -282,17 +312,19 @@ def test_routing(tname, native_calls):
     # covered: the native entry, with and without the image gradient
     for image_grad, path in ((True, "fi_bwd_lp:tiled_c3"), (False, "fi_bwd_lp:tiled_c3_noimage")):
         del native_calls[:]
-        lo, hi = _layer_grads(T, (2, 3, 24, 160), 4, image_grad)
+        lo, hi, _ = _layer_grads(T, (2, 3, 24, 160), 4, image_grad)
         assert native_calls == [(0, path)], native_calls
         for g_lo, g_hi in zip(lo, hi):
             assert (g_lo is None) == (g_hi is None) and (g_lo is None or torch.equal(g_lo, g_hi.to(T)))
-    # not covered: C = 4, W = 157, fs = 2 -- the widened path, untouched by the native entry (its image gradient takes
-    # fp32 atomics: held to the condition of test_image_gradient_matches_the_fp32_library)
+    # not covered: C = 4, W = 157, fs = 2 -- the widened path, untouched by the native entry (its image gradient is summed
+    # in an order the hardware picks: held to the condition of test_image_gradient_matches_the_fp32_library, with half an
+    # ulp_T more for the half layer's gradient, which is stored in T; only the RGB fs == 4 kernel has planes)
     for shape, fs in (((2, 4, 24, 160), 4), ((2, 3, 24, 157), 4), ((2, 3, 24, 160), 2)):
         del native_calls[:]
-        lo, hi = _layer_grads(T, shape, fs, True)
+        lo, hi, held = _layer_grads(T, shape, fs, True)
         assert native_calls == [], (shape, fs, native_calls)
-        image_gradients_agree(lo[0].float(), hi[0], T, "widened %s fs %d" % (shape, fs))
+        image_gradients_agree(lo[0].float(), hi[0], T, "widened %s fs %d" % (shape, fs),
+                              image_reference(*held, fs=fs, planes=shape[1] == 3 and fs == 4), stored=(True, False))
         for g_lo, g_hi in zip(lo[1:], hi[1:]):
             assert torch.equal(g_lo, g_hi.to(T)), (shape, fs)
     # the blend: both directions' backward launches (with the image gradient, as the float32 blend computes it)

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "memc-net_amd")):
+for _p in (ROOT, os.path.join(ROOT, "memc-net_amd"), os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
@@ -191,6 +191,19 @@ def test_fp16_overflow_goes_to_inf_like_a_cast(oracle, W):
 @pytest.mark.parametrize("tname", sorted(DTYPES))
 @pytest.mark.parametrize("C", [3, 4])
 def test_backward_is_the_fp32_backward_on_widened_inputs(tname, C):
+    """The half layer's gradients are the fp32 layer's on the widened inputs, rounded once: bit for bit for the flow and the
+    taps.  The image gradient is not reproducible from run to run on either side, so it cannot be asked to be bit-equal:
+      C = 4 (the half call widens on the host: the fp32 library twice).  fi_bwd_cn.hip's fi_bwd_image_owner stores every cell
+            once, without global atomics -- but the cell's list of (coefficient, site) entries is built with LDS atomics:
+            atomicCAS hands the head slot of a tap index to whichever site's lane gets there first, atomicAdd on the cell's
+            cursor (oc) orders the tail entries, and the replay sums `entry coefficient x gradoutput` with fmas in list
+            order, head slots, then the tails in segments.  That per-cell sum is order-dependent: last-bit differences in a
+            few per cent of the cells between two runs.
+      C = 3 (the half layer's native kernel against the fp32 one).  Both pack the same integers into the LDS planes; what
+            differs is the order in which pk_flush's global fp32 atomics of neighbouring tiles' overlapping boxes retire.
+    Rule (tests/_image_grad.py: float64 restatement `want`, derived per-cell `bound`; the planes' part only for C = 3): both
+    results lie within bound + ulp_T / 2 of want; they are bit-equal wherever no rounding boundary of T lies inside
+    want +- bound (a result within the bound then has one possible rounding); at most one ulp_T apart elsewhere."""
     from my_package.modules.FilterInterpolationModule import FilterInterpolationModule
     from my_package.modules.FilterInterpolationBlendModule import FilterInterpolationBlendModule
     T = DTYPES[tname]
@@ -210,7 +223,22 @@ def test_backward_is_the_fp32_backward_on_widened_inputs(tname, C):
     hi = run(torch.float32)
     for g_lo, g_hi, name in zip(lo, hi, ("image", "flow", "taps")):
         assert g_lo.dtype == T
-        assert torch.equal(g_lo, g_hi.to(T)), name
+        if name != "image":
+            assert torch.equal(g_lo, g_hi.to(T)), name
+    # the image gradient: the restatement of the operation on these inputs and its derived bound (tests/_image_grad.py)
+    import _image_grad as IG
+    ref = IG.Reference(widened(flow, T), widened(filt, T), widened(gout, T), fs=4, planes=C == 3)
+    lo1, hi1 = lo[0].double().cpu().numpy(), hi[0].to(T).double().cpu().numpy()
+    worst = [float(ref.ratio(g, st)[0].max()) for g, st in ((lo1, tname), (hi1, tname), (hi[0].double().cpu().numpy(), None))]
+    inside = ref.boundary_inside(tname)
+    apart = np.abs(lo1 - hi1) / IG.ulp_T(np.maximum(np.abs(lo1), np.abs(hi1)), tname)
+    print("image gradient C%d %s: max err / (bound + ulp_T / 2) %.3f (half layer) and %.3f (fp32 layer, rounded), fp32 layer before "
+          "rounding: max err / bound %.3f; a rounding boundary in reach of %.4f of the cells, %d of them differ, %d elsewhere"
+          % (C, tname, worst[0], worst[1], worst[2], float(inside.mean()), int((lo1 != hi1)[inside].sum()),
+             int((lo1 != hi1)[~inside].sum())))
+    assert max(worst) <= 1.0, worst
+    assert bool((lo1 == hi1)[~inside].all()), "image: different roundings where no rounding boundary of T is in reach"
+    assert float(apart[inside].max() if inside.any() else 0.0) <= 1.0, "image: more than one ulp_T apart"
     if C == 3:      # the blend as well
         o0 = rng.random((B, 1, H, W), dtype=np.float32)
         occs = (widened(o0, T), widened((1.0 - o0).astype(np.float32), T))

@@ -12,9 +12,11 @@ Rules, all taken over unchanged from the modules that own them:
                     a half rounding about once in 2^13 elements; the observed fraction is printed).  Outputs are pre-filled
                     with NaN: an unwritten site fails.
   backward          gradinput2 / gradinput3 bit-equal to the fp32 library's on the widened inputs, rounded (pre-filled with
-                    NaN on both sides: the kernels define them); gradinput1 through test_gpu_lowp_grad.image_gradients_agree
-                    (one ulp_T, 99.9 % equal) after the fp32 library run twice passed it; against the oracle: tests/_parity.py's
-                    rule plus half an ulp_T for a gradient stored in T.
+                    NaN on both sides: the kernels define them); gradinput1 through test_gpu_lowp_grad.image_gradients_agree:
+                    every finite cell of either side, before rounding, within tests/_image_grad.py's derived bound (the packed
+                    planes' grid plus fp32's roundings, whatever order the atomics retire in) of the float64 restatement on
+                    the call's inputs, and 99.9 % equal after rounding to T -- after the fp32 library run twice passed it;
+                    against the oracle: tests/_parity.py's rule plus half an ulp_T for a gradient stored in T.
   heavy tails       gradinput1 under the rules of test_gpu_parity.test_rgb_backward_packed_planes_heavy_tailed_tile, which the
                     fp32 library on the same widened inputs is held to first.
 Every figure is printed before it is asserted (`pytest -s`); profiles/lowp_paths_observed.md keeps one run's.
@@ -35,7 +37,7 @@ for _p in (ROOT, os.path.join(ROOT, "memc-net_amd"), _HERE):
 import _lowp_paths as LP                   # noqa: E402
 import _parity as P                        # noqa: E402
 import test_gpu_lowp_parity as FWD         # noqa: E402  (check, ulp, to_dev, widened)
-import test_gpu_lowp_grad as BWD           # noqa: E402  (image_gradients_agree, ulp)
+import test_gpu_lowp_grad as BWD           # noqa: E402  (image_gradients_agree, image_reference, ulp)
 from tools import synth                    # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -199,8 +201,9 @@ def test_backward_on_every_tile_path(oracle, ci, tname, with_image):
         if with_image:
             assert g1.dtype == torch.float32
             b1, _, _ = run_f32(x, flow, filt, gout, True)
-            BWD.image_gradients_agree(w1, b1, T, "control: fp32 twice, " + label)
-            BWD.image_gradients_agree(g1, w1, T, "native vs fp32, " + label)
+            ref = BWD.image_reference(flow, filt, gout)
+            BWD.image_gradients_agree(w1, b1, T, "control: fp32 twice, " + label, ref)
+            BWD.image_gradients_agree(g1, w1, T, "native vs fp32, " + label, ref)
         if ci in (0, 2):
             against_oracle(oracle, x, flow, filt, gout, (g1.to(T) if with_image else None, g2, g3), label)
 
@@ -317,5 +320,6 @@ def test_backward_nan_and_inf_inputs(tname):
             r1 = w1.to(T)
             assert 0 < int((~torch.isfinite(r1)).sum()) < 200
             b1, _, _ = run_f32(x, flow, filt, gout, True)
-            BWD.image_gradients_agree(w1, b1, T, "control: fp32 twice, NaN / Inf inputs %s" % tname)
-            BWD.image_gradients_agree(g1, w1, T, "native vs fp32, NaN / Inf inputs %s" % tname)
+            ref = BWD.image_reference(flow, filt, gout)
+            BWD.image_gradients_agree(w1, b1, T, "control: fp32 twice, NaN / Inf inputs %s" % tname, ref)
+            BWD.image_gradients_agree(g1, w1, T, "native vs fp32, NaN / Inf inputs %s" % tname, ref)
