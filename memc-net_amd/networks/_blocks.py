@@ -123,17 +123,24 @@ class _Upsample2x(nn.Module):
 # trunk of the filter / occlusion estimators: 'c<out>' = conv3x3 + ReLU, 'p' = 2x2 max-pool, 'u' = bilinear x2
 _TRUNK = ("c32 c32 c32 p  c64 c64 p  c128 c128 p  c256 c256 p  c512 c512 p  c512 c512 "
           "c512 u c256  c256 u c128  c128 u c64  c64 u c32  c32 u c16").split()
+# MEMC_Net_s's lighter trunk (networks/MEMC_Net_s.py:192-239 of the reference): one convolution per stage, 'b' = a batch
+# norm where the reference's conv_relu_maxpool / conv_relu_unpool put it -- behind the stage's ReLU
+TRUNK_S = ("c16  c32 b p  c64 b p  c128 b p  c256 b p  c512 b p  c512 "
+           "u c256 b  u c128 b  u c64 b  u c32 b  u c16 b").split()
 
 
-def unet_trunk(cin, align_corners, batch_norm=False):
+def unet_trunk(cin, align_corners, batch_norm=False, tokens=_TRUNK):
     """Flat list of modules (the reference extends a python list with Sequential objects, which flattens them:
     state-dict keys are indices into that flat list).  `batch_norm`: MEMC_Net normalises in front of every
-    pooling and upsampling layer (MEMC_Net.py:293-320); MEMC_Net_star has those lines commented out."""
+    pooling and upsampling layer (MEMC_Net.py:293-320); MEMC_Net_star has those lines commented out.  `tokens`: another
+    trunk than theirs, with its batch norms spelled out ('b')."""
     mods, ch = [], cin
-    for tok in _TRUNK:
+    for tok in tokens:
         if tok in ("p", "u") and batch_norm:
             mods.append(nn.BatchNorm2d(ch))
-        if tok == "p":
+        if tok == "b":
+            mods.append(nn.BatchNorm2d(ch))
+        elif tok == "p":
             mods.append(nn.MaxPool2d((2, 2)))
         elif tok == "u":
             mods.append(_Upsample2x(align_corners))

@@ -3,7 +3,7 @@
 scene directory, interpolate the frame between frame10.png and frame11.png and score it against the ground truth.
 
     python tools/demo_middlebury.py --data other-data --gt other-gt-interp --output results
-                                    [--model MEMC_Net_star --weights best.pth --align-corners] [--save-which 1]
+                                    [--model {MEMC_Net_star,MEMC_Net,MEMC_Net_s} --weights best.pth --align-corners] [--save-which 1]
                                     [--precision {fp32,bf16,fp16,autocast-bf16,autocast-fp16}]
                                     [--gpu-io] [--scenes-per-step N] [--ssim]
                                     [--first im1.png --second im3.png --middle im2.png]
@@ -34,7 +34,8 @@ def main(argv=None):
     ap.add_argument("--data", required=True, help="directory of scene directories holding frame10.png / frame11.png")
     ap.add_argument("--gt", default="", help="directory of scene directories holding frame10i11.png")
     ap.add_argument("--output", required=True)
-    ap.add_argument("--model", default="MEMC_Net_star", choices=["MEMC_Net_star", "MEMC_Net"])
+    ap.add_argument("--model", default="MEMC_Net_star", choices=["MEMC_Net_star", "MEMC_Net", "MEMC_Net_s"],
+                    help="MEMC_Net_s: the reference README's `demo_MiddleBury.py --netName MEMC_Net_s --pretrained MEMC-Net_s_best.pth`")
     ap.add_argument("--weights", default="")
     ap.add_argument("--align-corners", action="store_true",
                     help="bilinear upsampling as PyTorch 0.2 did it: what the published checkpoints were trained with")
