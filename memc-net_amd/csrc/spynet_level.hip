@@ -19,72 +19,34 @@
 #include "memc_common.hpp"
 #include "memc_tile.hpp"
 #include "memc_desc.hpp"
+#include "memc_spynet_level.hpp"
 #include "memc_spynet.h"
 
 namespace memc {
 
 thread_local const char *t_spynet_path = "";
 
-// ATen's area_pixel_compute_source_index (flow_prologue.hip's up_index restates the same rule): source index and weights
-// of destination index `dst` among `in` samples.  align_corners: index and weight come from the ROUNDED product -- the
-// barrier keeps the compiler from contracting `src - i0` into an fma off the unrounded one.  Without align_corners there is
-// nothing to guard, which is why the barrier is on one branch only: the scale is 0.5, so 0.5 * (dst + 0.5) - 0.5 is exact
-// however it is contracted.
-__device__ __forceinline__ void level_up_index(int dst, int in, float scale, bool align, int &i0, int &i1, float &l0, float &l1)
-{
-    float src = align ? scale * (float)dst : fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.0f);
-    if (align) asm volatile("" : "+v"(src));
-    i0 = min((int)src, in - 1);
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-    l0 = 1.0f - l1;
-}
-
-// the sample position along one axis, clamped; a NaN fails the first comparison and becomes -2
-__device__ __forceinline__ float level_position(int x, float f, int n, float k, bool align)
-{
-    float p = (float)x + f;
-    if (!align) p = p * k - 0.5f;
-    p = p > -2.0f ? p : -2.0f;
-    return p < (float)(n + 1) ? p : (float)(n + 1);
-}
-
-struct LevelRow {                              // what the sites of one output row share: the coarse rows and their weights
-    int o0, o1;                                // element offsets of coarse rows y0, y1
-    float l0, l1;
-};
-
-// One site: the doubled upsampled flow (ux, uy) and the three channels of `second` sampled at (x, y) + it.
+// One site: the doubled upsampled flow (ux, uy) and the three channels of `second` sampled at (x, y) + it.  The site
+// arithmetic (level_up_index, level_position, LevelRow, level_flow, level_corners) is memc_spynet_level.hpp's, shared with
+// the backward unit.
 __device__ __forceinline__ void level_site(int x, int y, int W, int H, int w, float sx, float kx, float ky, bool align_up,
                                            bool align_sample, const LevelRow &r, const float *__restrict__ cb, int64_t scc,
                                            const float *__restrict__ sb, int64_t ssc, int ssh, float &ux, float &uy,
                                            float (&warped)[3])
 {
-    int x0, x1;
-    float lx0, lx1;
-    level_up_index(min(x, 2 * w - 1), w, sx, align_up, x0, x1, lx0, lx1);      // a padded column repeats column 2w - 1
-    const float *c0 = cb, *c1 = cb + scc;
-    ux = 2.0f * (r.l0 * (lx0 * c0[r.o0 + x0] + lx1 * c0[r.o0 + x1]) + r.l1 * (lx0 * c0[r.o1 + x0] + lx1 * c0[r.o1 + x1]));
-    uy = 2.0f * (r.l0 * (lx0 * c1[r.o0 + x0] + lx1 * c1[r.o0 + x1]) + r.l1 * (lx0 * c1[r.o1 + x0] + lx1 * c1[r.o1 + x1]));
-
+    level_flow(x, w, sx, align_up, r, cb, scc, ux, uy);
     const float px = level_position(x, ux, W, kx, align_sample), py = level_position(y, uy, H, ky, align_sample);
-    const float fx0 = floorf(px), fy0 = floorf(py);
-    const int ix = (int)fx0, iy = (int)fy0;                                    // within [-2, W + 1], [-2, H + 1]
-    const float ax = px - fx0, ay = py - fy0, bx = (fx0 + 1.0f) - px, by = (fy0 + 1.0f) - py;
-    const bool inx0 = ix >= 0 && ix < W, inx1 = ix + 1 >= 0 && ix + 1 < W;
-    const bool iny0 = iy >= 0 && iy < H, iny1 = iy + 1 >= 0 && iy + 1 < H;
-    const int cx0 = clampi(ix, W - 1), cx1 = clampi(ix + 1, W - 1);
-    const int r0 = clampi(iy, H - 1) * ssh, r1 = clampi(iy + 1, H - 1) * ssh;
-    const float wnw = bx * by, wne = ax * by, wsw = bx * ay, wse = ax * ay;
+    const LevelCorners k = level_corners(px, py, W, H, ssh);
+    const float wnw = k.bx * k.by, wne = k.ax * k.by, wsw = k.bx * k.ay, wse = k.ax * k.ay;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         const float *p = sb + c * ssc;
-        const float nw = p[r0 + cx0], ne = p[r0 + cx1], sw = p[r1 + cx0], se = p[r1 + cx1];
+        const float nw = p[k.r0 + k.cx0], ne = p[k.r0 + k.cx1], sw = p[k.r1 + k.cx0], se = p[k.r1 + k.cx1];
         float v = 0.0f;
-        v += inx0 && iny0 ? nw * wnw : 0.0f;
-        v += inx1 && iny0 ? ne * wne : 0.0f;
-        v += inx0 && iny1 ? sw * wsw : 0.0f;
-        v += inx1 && iny1 ? se * wse : 0.0f;
+        v += k.inx0 && k.iny0 ? nw * wnw : 0.0f;
+        v += k.inx1 && k.iny0 ? ne * wne : 0.0f;
+        v += k.inx0 && k.iny1 ? sw * wsw : 0.0f;
+        v += k.inx1 && k.iny1 ? se * wse : 0.0f;
         warped[c] = v;
     }
 }

@@ -17,14 +17,24 @@ with first, second [B, 3, H, W] and coarse [B, 2, h, w], H in {2h, 2h + 1}, W in
 exactly the combination (False, True); the unmodified reference under a current PyTorch computes (False, False), the
 PyTorch 0.2 its checkpoints were trained with (True, True).
 
-The kernel serves inference in float32.  The torch expression (`_composed`, the exact composed route) runs instead
+The forward kernel serves float32.  The torch expression (`_composed`, the exact composed route) runs instead
   * on CPU tensors, on other dtypes than float32 and under autocast,
   * where the library declines the call (planes beyond 32-bit offsets, a w-stride other than 1),
   * with the class attribute `fused` set to False,
-  * whenever gradients are enabled and an input requires one: there is NO BACKWARD KERNEL -- such a call keeps torch's
-    autograd through the composed route.  (In a training step of SPyNet that is every level but the coarsest: its frames
-    are data and its coarse flow is zeros, no input wants a gradient, its output is constant with respect to the
-    parameters, and it takes the kernel.)
+  * whenever gradients are enabled and an input requires one -- such a call keeps torch's autograd through the composed
+    route -- UNLESS `native_backward` is set and the gradient wanted is the one a training step of SPyNet needs: `coarse`
+    requires one, `second` does not.  (In such a step that is every level but the coarsest: its frames are data and its
+    coarse flow is zeros, no input wants a gradient, its output is constant with respect to the parameters, and it takes
+    the forward kernel alone.)
+
+The backward kernel (libmemc_hip_spynet_grad.so, include/memc_spynet_grad.h): with `native_backward = True` such a call goes
+through a `torch.autograd.Function` whose forward is the forward kernel's call and whose backward is one launch for the
+gradient of `coarse` -- frames that are data: no image gradient, no atomics, the same bits from run to run; the gradient of
+`first` is gradoutput[:, 0:3], `second` gets none.  It saves `second` and `coarse`, not the output.  Where either library
+declines, the Function composes: the forward returns `_composed`'s values, the backward recomputes `_composed` under
+`enable_grad` and takes torch's gradient.  `native_backward` ships False (profiles/r27_spynet_level_backward.txt is what a
+change of the default will rest on): a call where `second` requires a gradient, and every call while it is False, keep the
+torch expression.
 Values: the upsampled flow and the copy of `first` equal the composed route's to within fp32 rounding (bit for bit where the
 arithmetic is exact); the warp computes the sample position directly instead of through grid_sample's normalise /
 un-normalise round trip, the same function to within fp32 rounding (tests/test_spynet_level_spec.py).
@@ -33,6 +43,7 @@ import torch
 import torch.nn.functional as F
 
 import my_package._ext.my_lib_spynet as my_lib_spynet
+import my_package._ext.my_lib_spynet_grad as my_lib_spynet_grad
 from ._common import declined
 
 
@@ -53,11 +64,46 @@ def _composed(first, second, coarse, align_upsample, align_sample):
     return torch.cat([first, warped, up], 1)
 
 
+class _SpyNetLevelFunction(torch.autograd.Function):
+    """The level input with the gradient of `coarse` by libmemc_hip_spynet_grad.so; `second` gets no gradient (the layer
+    sends no call here whose `second` requires one)."""
+
+    @staticmethod
+    def forward(ctx, first, second, coarse, align_upsample, align_sample):
+        ctx.flags = (align_upsample, align_sample)
+        ctx.save_for_backward(second, coarse)
+        out = first.new_empty((first.size(0), 8, first.size(2), first.size(3)))
+        err = my_lib_spynet.SpyNetLevelLayer_gpu_forward(first, second, coarse, out, align_upsample, align_sample)
+        if declined(err, "SpyNetLevelLayer_gpu_forward"):
+            return _composed(first, second, coarse, align_upsample, align_sample)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gradoutput):
+        second, coarse = ctx.saved_tensors
+        gradfirst = gradoutput[:, 0:3] if ctx.needs_input_grad[0] else None
+        gradcoarse = None
+        if ctx.needs_input_grad[2]:
+            if gradoutput.stride(3) != 1:              # sum().backward() hands over an expanded one
+                gradoutput = gradoutput.contiguous()
+            gradcoarse = torch.empty_like(coarse, memory_format=torch.contiguous_format)
+            err = my_lib_spynet_grad.SpyNetLevelLayer_gpu_backward(second, coarse, gradoutput, gradcoarse, *ctx.flags)
+            if declined(err, "SpyNetLevelLayer_gpu_backward"):
+                with torch.enable_grad():
+                    c = coarse.detach().requires_grad_(True)
+                    first = torch.zeros_like(second)   # out[:, 0:3] is a copy: it carries nothing to `coarse`
+                    gradcoarse, = torch.autograd.grad(_composed(first, second, c, *ctx.flags), c, gradoutput)
+        return gradfirst, None, gradcoarse, None, None
+
+
 class SpyNetLevelLayer(object):
     """`SpyNetLevelLayer(align_upsample, align_sample)(first, second, coarse)` returns the level's [B, 8, H, W] input.
-    Forward only: a call that needs gradients takes the torch expression and torch's autograd."""
+    A call that needs gradients takes the torch expression and torch's autograd, unless `native_backward` is set and the
+    gradient wanted is that of `coarse` (and of `first`) alone."""
 
     fused = True                                   # False: the torch expression for every call
+    native_backward = False                        # True: the gradient of `coarse` by libmemc_hip_spynet_grad.so
 
     def __init__(self, align_upsample=False, align_sample=False):
         self.align_upsample, self.align_sample = bool(align_upsample), bool(align_sample)
@@ -69,6 +115,13 @@ class SpyNetLevelLayer(object):
             return False
         return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
 
+    def _backward_kernel_serves(self, first, second, coarse):
+        if not (self.fused and self.native_backward) or torch.is_autocast_enabled() or not torch.is_grad_enabled():
+            return False
+        if not all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 for t in (first, second, coarse)):
+            return False
+        return coarse.requires_grad and not second.requires_grad
+
     def __call__(self, first, second, coarse):
         if self._kernel_serves((first, second, coarse)):
             out = first.new_empty((first.size(0), 8, first.size(2), first.size(3)))
@@ -76,6 +129,8 @@ class SpyNetLevelLayer(object):
                                                              self.align_sample)
             if not declined(err, "SpyNetLevelLayer_gpu_forward"):
                 return out
+        elif self._backward_kernel_serves(first, second, coarse):
+            return _SpyNetLevelFunction.apply(first, second, coarse, self.align_upsample, self.align_sample)
         return _composed(first, second, coarse, self.align_upsample, self.align_sample)
 
     forward = __call__

@@ -16,7 +16,11 @@ Differences, deliberate:
   * `align_upsample` / `align_sample`: the `align_corners` of the x2 upsampling and of `grid_sample`, explicit;
   * `fused_level`: a level's 8-channel input by one kernel (my_package.modules.SpyNetLevelModule, an extension of this
     repository's my_package) instead of nine or ten ATen launches, where that kernel serves the call: float32 CUDA tensors,
-    no autocast, no gradient wanted.
+    no autocast, no gradient wanted;
+  * `fused_level_backward`: in a training step, where a level's coarse flow wants a gradient and its frames are data, the
+    level input through the same layer's autograd Function -- the forward kernel, and one backward kernel for the gradient
+    of the coarse flow (libmemc_hip_spynet_grad.so) instead of torch's autograd through the torch expression.  Off by
+    default.
 """
 import torch
 import torch.nn as nn
@@ -87,15 +91,21 @@ class SPyNet(nn.Module):
         # the coarsest, whose frames and zero flow want none), autocast and other dtypes than float32 take the torch
         # expression whatever this says
         self.fused_level = True
+        # the gradient of a level's coarse flow by one kernel (my_package.functions.SpyNetLevelLayer.native_backward) instead
+        # of torch's autograd through the torch expression.  Ships off whatever profiles/r27_spynet_level_backward.txt says:
+        # the default training route is the one the existing tests pin
+        self.fused_level_backward = False
         self.moduleBasic = nn.ModuleList([_Basic() for _ in range(LEVELS)])
 
     def level_input(self, first, second, coarse):
         """The [B, 8, H, W] input of one level's convolutions, by the route `fused_level` selects: the only place it is made.
         With my_package's extension it is the layer's business either way (its kernel, or its own torch expression for CPU
-        tensors, other dtypes, autocast, declined calls, inputs that want a gradient and `fused_level = False`)."""
+        tensors, other dtypes, autocast, declined calls, inputs that want a gradient and `fused_level = False`; with
+        `fused_level_backward` its backward kernel where only the coarse flow wants a gradient)."""
         if SpyNetLevelModule is not None:
             level = SpyNetLevelModule(self.align_upsample, self.align_sample)
             level.f.fused = bool(self.fused_level)
+            level.f.native_backward = bool(self.fused_level_backward)
             return level(first, second, coarse)
         return level_input_composed(first, second, coarse, self.align_upsample, self.align_sample)
 
