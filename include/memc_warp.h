@@ -62,7 +62,15 @@
  *     contributions of an ordinary cell.  Sites beyond that bound, and sites with an Inf / NaN input, add with fp32
  *     atomics exactly as the reference does (my_lib_kernel.cu:1276-1288); four and more channels never round;
  *   - return 0 on success, -1 on a failed shape/stride check or a launch error (my_lib_cuda.c:611-646,
- *     my_lib_kernel.cu:1559-1566).
+ *     my_lib_kernel.cu:1559-1566);
+ *   - Limits.  Every size and stride fits `int` (the launchers' parameter type).  Batch and channel offsets are formed in
+ *     64 bits: a tensor may span any number of elements.  Inside ONE plane the last element's offset,
+ *     (H - 1) * row_stride + W, must not exceed INT32_MAX elements, for EVERY tensor of a call: the one-lane-per-site,
+ *     any-filter-size and one-site kernels form `row * row_stride` in int.  A layer entry point refuses a view beyond that
+ *     with -1, before anything is launched (a view of 600 rows that lie 2^22 floats apart, say); the kernel launchers
+ *     below take the reference's `int` strides and leave this limit to their caller.  Below it, the tiled kernels address
+ *     a plane with 32-bit BYTE offsets where ((H - 1) * row_stride + W) * 4 < 2^32 and the call goes to the 64-bit
+ *     families ("direct", "scalar", "general") otherwise -- same results.
  *
  * No torch, HIP or C++ types appear in this header; a HIP stream is passed as an opaque pointer
  * (`hipStream_t` is itself a pointer type; 0 / NULL is the default stream).

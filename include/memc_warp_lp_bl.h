@@ -21,9 +21,11 @@
  *     add): the caller zero-fills it and rounds it to T afterwards.  As in the fp32 library it is not bit-reproducible
  *     from run to run where more than one order of the adds rounds differently.
  *
- * Forward: any well-formed call is served.  The tiled kernels ("bl_fwd_lp:tiled_c3" for C == 3, "bl_fwd_lp:tiled_chunks"
- * for any other channel count) take the coverage below; everything else -- any width, stride and alignment -- takes the
- * one-lane-per-site kernel ("bl_fwd_lp:direct").
+ * Forward: any well-formed call is served whose planes lie within int ELEMENT offsets -- (H - 1) * input1's row stride
+ * + W at most INT32_MAX: every forward kernel forms a site's four source offsets as `row * row_stride + column` in int; a
+ * view beyond that returns 1 with nothing touched (the flow's offsets are 64-bit: its row stride has no limit).  The tiled
+ * kernels ("bl_fwd_lp:tiled_c3" for C == 3, "bl_fwd_lp:tiled_chunks" for any other channel count) take the coverage
+ * below; everything else -- any width, stride and alignment -- takes the one-lane-per-site kernel ("bl_fwd_lp:direct").
  *
  * Backward: C == 3 inside the coverage below ("bl_bwd_lp:tiled_c3"); every other well-formed call returns 1 with nothing
  * touched: the caller widens to float32 and takes InterpolationLayer_gpu_backward.
@@ -36,12 +38,13 @@
  * gradinput1 have input1's shape and layout, gradinput2 input2's.  The Interpolation entry points insist on C == 3, the
  * InterpolationCh ones take any channel count.
  *
- * Return: 0 enqueued (an empty batch enqueues nothing and returns 0); 1 (backward only) a well-formed call outside the
- * coverage -- nothing is touched or enqueued; -1 a failed descriptor check (before the device is touched: a payload dtype
- * that is not F16 / BF16, a flow dtype that is neither F32 nor the payload's, a null descriptor or null data, negative or
- * beyond-int32 sizes and strides, a w-stride other than 1, a flow that is not [B, 2, H, W], an output / gradoutput /
- * gradinput1 / gradinput2 of another shape or layout, Interpolation with C != 3) or a launch error.  Work is enqueued
- * asynchronously on `stream`; nothing is allocated, synchronised or kept between calls; every call is stream-capturable.
+ * Return: 0 enqueued (an empty batch enqueues nothing and returns 0); 1 a well-formed call outside the coverage (the
+ * backward's; the forward: only a plane beyond int element offsets) -- nothing is touched or enqueued; -1 a failed
+ * descriptor check (before the device is touched: a payload dtype that is not F16 / BF16, a flow dtype that is neither
+ * F32 nor the payload's, a null descriptor or null data, negative or beyond-int32 sizes and strides, a w-stride other
+ * than 1, a flow that is not [B, 2, H, W], an output / gradoutput / gradinput1 / gradinput2 of another shape or layout,
+ * Interpolation with C != 3) or a launch error.  Work is enqueued asynchronously on `stream`; nothing is allocated,
+ * synchronised or kept between calls; every call is stream-capturable.
  */
 #ifndef MEMC_WARP_LP_BL_H
 #define MEMC_WARP_LP_BL_H

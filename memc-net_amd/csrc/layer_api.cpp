@@ -16,6 +16,16 @@ namespace {
 using namespace memc;            // the descriptor checks: memc_desc.hpp
 constexpr int kErr = -1;
 
+// Beyond memc_desc.hpp's ok(): the one-lane-per-site, any-filter-size and one-site kernels of this library form a row
+// offset as `row * row_stride` in int, and the tiled ones fall back to them, so every plane's last element,
+// (h - 1) * row_stride + w, must lie within INT32_MAX elements (include/memc_warp.h, "Limits").  A view beyond that is
+// refused (-1) before anything is launched.
+inline bool rows_fit_int(const memc_tensor4 *t)
+{
+    return t->size[2] <= 1 || (t->size[2] - 1) * t->stride[2] + t->size[3] <= (int64_t)INT32_MAX;
+}
+inline bool okp(const memc_tensor4 *t) { return ok(t) && rows_fit_int(t); }
+
 inline int nelem(const memc_tensor4 *t) { return (int)numel(t); }   // ignored by the launchers
 
 #define S4(t) (int)(t)->stride[0], (int)(t)->stride[1], (int)(t)->stride[2], (int)(t)->stride[3]
@@ -23,7 +33,7 @@ inline int nelem(const memc_tensor4 *t) { return (int)numel(t); }   // ignored b
 int bilinear_forward(bool require_c3, memc_stream_t stream, const memc_tensor4 *input1,
                      const memc_tensor4 *input2, const memc_tensor4 *output)
 {
-    if (!ok(input1) || !ok(input2) || !ok(output)) return kErr;
+    if (!okp(input1) || !okp(input2) || !okp(output)) return kErr;
     if (require_c3 && input1->size[1] != 3) return kErr;                       // my_lib_cuda.c:373
     if (!flow_matches(input1, input2)) return kErr;                            // :375-381
     if (!same_layout(input1, output)) return kErr;                             // :397-398 (+h, w)
@@ -36,7 +46,7 @@ int bilinear_backward(bool require_c3, memc_stream_t stream, const memc_tensor4 
                       const memc_tensor4 *input2, const memc_tensor4 *gradoutput,
                       const memc_tensor4 *gradinput1, const memc_tensor4 *gradinput2)
 {
-    if (!ok(input1) || !ok(input2) || !ok(gradoutput) || !ok(gradinput1) || !ok(gradinput2)) return kErr;
+    if (!okp(input1) || !okp(input2) || !okp(gradoutput) || !okp(gradinput1) || !okp(gradinput2)) return kErr;
     if (require_c3 && input1->size[1] != 3) return kErr;                       // my_lib_cuda.c:430
     if (!flow_matches(input1, input2)) return kErr;                            // :432-438
     if (!same_layout(input1, gradinput1) || !same_layout(input2, gradinput2)) return kErr;   // :455-458
@@ -93,7 +103,7 @@ int FilterInterpolationLayer_gpu_forward(memc_stream_t stream, const memc_tensor
                                          const memc_tensor4 *input2, const memc_tensor4 *input3,
                                          const memc_tensor4 *output)
 {
-    if (!ok(input1) || !ok(input2) || !ok(input3) || !ok(output)) return kErr;    // my_lib_cuda.c:641-643
+    if (!okp(input1) || !okp(input2) || !okp(input3) || !okp(output)) return kErr;    // my_lib_cuda.c:641-643
     if (!flow_matches(input1, input2)) return kErr;                                 // :611-617
     if (!taps_match(input1, input3)) return kErr;
     const int filter_size = (int)sqrt((float)input3->size[1]);                      // :619-620
@@ -111,8 +121,8 @@ int FilterInterpolationLayer_gpu_backward(memc_stream_t stream, const memc_tenso
                                           const memc_tensor4 *gradinput2, const memc_tensor4 *gradinput3)
 {
     // EXTENSION: gradinput1 == NULL -- the caller does not want the image gradient (include/memc_warp.h)
-    if (!ok(input1) || !ok(input2) || !ok(input3) || !ok(gradoutput) || (gradinput1 && !ok(gradinput1)) ||
-        !ok(gradinput2) || !ok(gradinput3))
+    if (!okp(input1) || !okp(input2) || !okp(input3) || !okp(gradoutput) || (gradinput1 && !okp(gradinput1)) ||
+        !okp(gradinput2) || !okp(gradinput3))
         return kErr;                                                                // :716-718
     if (!flow_matches(input1, input2)) return kErr;                                 // :685-691
     if (!taps_match(input1, input3)) return kErr;
@@ -138,7 +148,7 @@ int FilterInterpolationBlendLayer_gpu_forward(memc_stream_t stream, const memc_t
 {
     const memc_tensor4 *all[] = {input0, input2, flow0, flow1, filter0, filter1, occlusion0, occlusion1, output};
     for (const memc_tensor4 *t : all)
-        if (!ok(t)) return kErr;
+        if (!okp(t)) return kErr;
     if (!flow_matches(input0, flow0)) return kErr;
     if (!same_layout(input0, input2) || !same_layout(input0, output) || !same_layout(flow0, flow1) ||
         !same_layout(filter0, filter1) || !same_layout(occlusion0, occlusion1))
@@ -165,10 +175,10 @@ int FilterInterpolationCtxLayer_gpu_forward(memc_stream_t stream, const memc_ten
 {
     const memc_tensor4 *need[] = {image, context, flow, filter, image_out, context_out};
     for (const memc_tensor4 *t : need)
-        if (!ok(t)) return kErr;
+        if (!okp(t)) return kErr;
     const bool blend = prev != nullptr;
     if (blend != (occlusion_prev != nullptr) || blend != (occlusion_this != nullptr)) return kErr;
-    if (blend && (!ok(prev) || !ok(occlusion_prev) || !ok(occlusion_this))) return kErr;
+    if (blend && (!okp(prev) || !okp(occlusion_prev) || !okp(occlusion_this))) return kErr;
     if (image->size[1] != 3 || !flow_matches(image, flow) || !flow_matches(context, flow)) return kErr;
     if (!same_layout(image, image_out) || !same_layout(context, context_out)) return kErr;
     if (!taps_match(image, filter)) return kErr;
@@ -193,7 +203,7 @@ int FilterInterpolationCtxLayer_gpu_forward(memc_stream_t stream, const memc_ten
 int FlowUpsample4Layer_gpu_forward(memc_stream_t stream, const memc_tensor4 *input, const memc_tensor4 *output,
                                    float mul, float div, int align_corners)
 {
-    if (!ok(input) || !ok(output)) return kErr;
+    if (!okp(input) || !okp(output)) return kErr;
     if (output->size[0] != input->size[0] || output->size[1] != input->size[1] ||
         output->size[2] != 4 * input->size[2] || output->size[3] != 4 * input->size[3])
         return kErr;
@@ -213,7 +223,7 @@ static bool count_matches(const memc_tensor4 *flow, const memc_tensor4 *count)
 int FlowProjectionLayer_gpu_forward(memc_stream_t stream, const memc_tensor4 *input1,
                                     const memc_tensor4 *count, const memc_tensor4 *output, int fillhole)
 {
-    if (!ok(input1) || !ok(count) || !ok(output)) return kErr;
+    if (!okp(input1) || !okp(count) || !okp(output)) return kErr;
     if (input1->size[1] != 2) return kErr;                                          // my_lib_cuda.c:762
     if (!count_matches(input1, count)) return kErr;
     if (!same_layout(input1, output)) return kErr;                                  // :781-782 (+h)
@@ -225,7 +235,7 @@ int FlowProjectionLayer_gpu_forward(memc_stream_t stream, const memc_tensor4 *in
 int FlowProjectionLayer_gpu_forward_ws(memc_stream_t stream, const memc_tensor4 *input1, const memc_tensor4 *count,
                                        const memc_tensor4 *output, int fillhole, void *workspace, size_t workspace_bytes)
 {
-    if (!ok(input1) || !ok(count) || !ok(output) || !workspace) return kErr;
+    if (!okp(input1) || !okp(count) || !okp(output) || !workspace) return kErr;
     if (input1->size[1] != 2) return kErr;
     if (!count_matches(input1, count)) return kErr;
     if (!same_layout(input1, output)) return kErr;
@@ -239,7 +249,7 @@ int FlowProjectionLayer_gpu_backward(memc_stream_t stream, const memc_tensor4 *i
                                      const memc_tensor4 *count, const memc_tensor4 *gradoutput,
                                      const memc_tensor4 *gradinput1)
 {
-    if (!ok(input1) || !ok(count) || !ok(gradoutput) || !ok(gradinput1)) return kErr;
+    if (!okp(input1) || !okp(count) || !okp(gradoutput) || !okp(gradinput1)) return kErr;
     if (input1->size[1] != 2) return kErr;                                          // :811
     if (!count_matches(input1, count)) return kErr;                                 // :813-817
     if (!same_layout(input1, gradinput1)) return kErr;                              // :835-836
@@ -254,7 +264,7 @@ int DepthFlowProjectionLayer_gpu_forward(memc_stream_t stream, const memc_tensor
                                          const memc_tensor4 *input2, const memc_tensor4 *count,
                                          const memc_tensor4 *output, int fillhole)
 {
-    if (!ok(input1) || !ok(input2) || !ok(count) || !ok(output)) return kErr;
+    if (!okp(input1) || !okp(input2) || !okp(count) || !okp(output)) return kErr;
     if (input1->size[1] != 2) return kErr;                                          // :868
     if (input2->size[1] != 1) return kErr;                                          // :870
     if (!count_matches(input1, input2) || !count_matches(input1, count)) return kErr;
@@ -270,7 +280,7 @@ int DepthFlowProjectionLayer_gpu_forward_ws(memc_stream_t stream, const memc_ten
                                             const memc_tensor4 *output, int fillhole, void *workspace,
                                             size_t workspace_bytes)
 {
-    if (!ok(input1) || !ok(input2) || !ok(count) || !ok(output) || !workspace) return kErr;
+    if (!okp(input1) || !okp(input2) || !okp(count) || !okp(output) || !workspace) return kErr;
     if (input1->size[1] != 2) return kErr;
     if (input2->size[1] != 1) return kErr;
     if (!count_matches(input1, input2) || !count_matches(input1, count)) return kErr;
@@ -286,8 +296,8 @@ int DepthFlowProjectionLayer_gpu_backward(memc_stream_t stream, const memc_tenso
                                           const memc_tensor4 *output, const memc_tensor4 *gradoutput,
                                           const memc_tensor4 *gradinput1, const memc_tensor4 *gradinput2)
 {
-    if (!ok(input1) || !ok(input2) || !ok(count) || !ok(output) || !ok(gradoutput) || !ok(gradinput1) ||
-        !ok(gradinput2))
+    if (!okp(input1) || !okp(input2) || !okp(count) || !okp(output) || !okp(gradoutput) || !okp(gradinput1) ||
+        !okp(gradinput2))
         return kErr;
     if (input1->size[1] != 2) return kErr;                                          // :929
     if (input2->size[1] != 1) return kErr;                                          // :933

@@ -458,6 +458,9 @@ static int bl_lp_forward(bool require_c3, hipStream_t stream, memc_dtype payload
     // empty (0)
     const int n = (int)input1->size[0], c = (int)input1->size[1], h = (int)input1->size[2], w = (int)input1->size[3];
     if (n == 0 || c == 0 || h == 0 || w == 0) return 0;
+    // coverage (1): every forward kernel forms the row offsets of a site's four source pixels in int ELEMENTS of input1's
+    // layout (row * row_stride + column); the flow's offsets are 64-bit
+    if ((int64_t)(h - 1) * input1->stride[2] + w > (int64_t)INT32_MAX) return kNotCovered;
     const bool tiled = bl_lp_tiled_ok(w, flowt, {input1, output}, {input2});
     return fi_dispatch(payload, flowt, [&](auto p, auto ft) {
         using T = decltype(p);
