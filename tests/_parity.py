@@ -14,6 +14,10 @@ that cancels to 3 from terms of 1e3 carries 2e-4 of noise in ANY fp32 evaluation
 evaluation on such inputs, the reference's own kernel 1.2e-4 from the oracle (tools/probes/depth_bwd_cancellation.py,
 profiles/r06_fresh_seed_sweeps.txt: the one case in 2100 fresh random shapes that found this, flow of +-160 px on a 90 x 130
 image).  With cancel = c the absolute bound of every cell is max(1e-4, c * max|want| over the tensor); only those checks pass one (3e-7).
+That term is no longer what binds gradinput2: tests/_proj_bound.py restates the projection operators in float64 and derives a
+bound PER CELL from the kernels' sources (12 u x the sum of the cell's |terms|, nothing fitted, no per-tensor term), and
+tests/test_gpu_proj_bound.py and the two random sweeps of tests/test_gpu_parity.py hold every projection output to it.  `cancel`
+remains only as the older, looser cap, its number unchanged.
 
 Every check appends one JSON line to gpurun_out/parity_errors.jsonl (MEMC_PARITY_LOG overrides the path): the test id,
 what was compared, the largest absolute error, the largest |want|, and the largest relative error among the elements

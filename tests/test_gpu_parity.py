@@ -16,6 +16,7 @@ import torch
 import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _parity as P                        # noqa: E402
+import _proj_bound as PB                   # noqa: E402
 from tools import synth                    # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -1847,6 +1848,20 @@ def test_flow_upsample4(shape, align):
     assert float((fr.grad - ft.grad).abs().max()) <= 1e-5 * max(1.0, float(ft.grad.abs().max()))
 
 
+def per_cell(r_ok, what):
+    """tests/_proj_bound.py: |got - want| within the bound derived per cell from the kernels' sources (err / bound <= 1)"""
+    r, ok = r_ok
+    worst = float(r[ok].max()) if ok.any() else 0.0
+    assert worst <= 1.0, "%s: err / per-cell bound %.3f" % (what, worst)
+
+
+def _projection_references(d):
+    """the float64 restatements of a case's projection forwards and, from the oracle's fill-0 planes, of its backwards"""
+    fw = {False: PB.Forward(d["flow"]), True: PB.Forward(d["flow"], d["depth"])}
+    assert fw[False].excluded == 0 and fw[True].excluded == 0
+    return fw
+
+
 def _random_shape_cases(n, seed):
     """Seeded random shapes: batch 1-3, channels 1-9 (+ 16 / 64 now and then), heights 1-90, widths 1-260 of every residue
     mod 4, a flow kind and scale per case -- every operator sees widths below one quad, ragged widths, partial tiles in both
@@ -1926,27 +1941,37 @@ def test_random_shapes_every_operator_forward_and_backward(oracle, case):
     w1, w2 = oracle.interpolation_ch_backward(d["x"], d["flow"], d["gout"])
     close(N(g1), w1, "Interpolation bwd gradinput1", 3 * RTOL)
     close(N(g2), w2, "Interpolation bwd gradinput2")
-    # FlowProjection / DepthFlowProjection, with and without hole filling, and their backward passes
+    # FlowProjection / DepthFlowProjection, with and without hole filling, and their backward passes -- beside the 1e-4 rule,
+    # every output within the per-cell bound of tests/_proj_bound.py (the binding check; gradinput2 without a per-tensor term)
+    ref = _projection_references(d)
     for fill in (0, 1):
         cnt, po = junk(B, 1, H, W), junk(B, 2, H, W)
         assert my_lib.FlowProjectionLayer_gpu_forward(f, cnt, po, fill) == 0
         want_out, want_cnt = oracle.flow_projection_forward(d["flow"], fill)
         assert np.array_equal(N(cnt), want_cnt), "FlowProjection count, fill %d" % fill
         close(N(po), want_out, "FlowProjection fwd, fill %d" % fill)
+        per_cell(ref[False].ratio_count(N(cnt)), "FlowProjection count, fill %d" % fill)
+        per_cell(ref[False].ratio_out(N(po), fill), "FlowProjection fwd, fill %d" % fill)
         dcnt, dpo = junk(B, 1, H, W), junk(B, 2, H, W)
         assert my_lib.DepthFlowProjectionLayer_gpu_forward(f, dep, dcnt, dpo, fill) == 0
         want_dout, want_dcnt = oracle.depth_flow_projection_forward(d["flow"], d["depth"], fill)
         close(N(dcnt), want_dcnt, "DepthFlowProjection count, fill %d" % fill)
         close(N(dpo), want_dout, "DepthFlowProjection fwd, fill %d" % fill)
+        per_cell(ref[True].ratio_count(N(dcnt)), "DepthFlowProjection count, fill %d" % fill)
+        per_cell(ref[True].ratio_out(N(dpo), fill), "DepthFlowProjection fwd, fill %d" % fill)
         if fill == 0:                                          # (backward sees the planes of a forward without hole filling)
             gin = junk(B, 2, H, W)
             assert my_lib.FlowProjectionLayer_gpu_backward(f, T(want_cnt), gf, gin) == 0
             close(N(gin), oracle.flow_projection_backward(d["flow"], want_cnt, d["gflow"]), "FlowProjection bwd")
+            per_cell(PB.Backward(d["flow"], None, want_cnt, None, d["gflow"]).ratio1(N(gin)), "FlowProjection bwd")
             gin, gd = junk(B, 2, H, W), junk(B, 1, H, W)
             assert my_lib.DepthFlowProjectionLayer_gpu_backward(f, dep, T(want_dcnt), T(want_dout), gf, gin, gd) == 0
             wg1, wg2 = oracle.depth_flow_projection_backward(d["flow"], d["depth"], want_dcnt, want_dout, d["gflow"])
             close(N(gin), wg1, "DepthFlowProjection bwd gradinput1")
             close(N(gd), wg2, "DepthFlowProjection bwd gradinput2", cancel=P.CANCEL)
+            bw = PB.Backward(d["flow"], d["depth"], want_dcnt, want_dout, d["gflow"])
+            per_cell(bw.ratio1(N(gin)), "DepthFlowProjection bwd gradinput1")
+            per_cell(bw.ratio2(N(gd)), "DepthFlowProjection bwd gradinput2")
 
 
 @pytest.mark.parametrize("case", RANDOM_CASES[:_N_STRIDED], ids=["%dx%dx%dx%d-%s-%g" % c[:6] for c in RANDOM_CASES[:_N_STRIDED]])
@@ -2010,6 +2035,7 @@ def test_random_strided_views_every_operator(oracle, case):
     close(N(g1), w1, "Interpolation bwd gradinput1 on views", 3 * RTOL)
     close(N(g2), w2, "Interpolation bwd gradinput2 on views")
     assert untouched(out_b, C) and untouched(g1_b, C) and untouched(g2_b, 2)
+    ref = _projection_references(d)
     for fill in (0, 1):
         cnt, cnt_b = window(1, fill=7.0)
         po, po_b = window(2, fill=7.0)
@@ -2017,17 +2043,21 @@ def test_random_strided_views_every_operator(oracle, case):
         want_out, want_cnt = oracle.flow_projection_forward(d["flow"], fill)
         assert np.array_equal(N(cnt), want_cnt), "FlowProjection count on views, fill %d" % fill
         close(N(po), want_out, "FlowProjection fwd on views, fill %d" % fill)
+        per_cell(ref[False].ratio_out(N(po), fill), "FlowProjection fwd on views, fill %d" % fill)
         dcnt, dcnt_b = window(1, fill=7.0)
         dpo, dpo_b = window(2, fill=7.0)
         assert my_lib.DepthFlowProjectionLayer_gpu_forward(f, dep, dcnt, dpo, fill) == 0
         want_dout, want_dcnt = oracle.depth_flow_projection_forward(d["flow"], d["depth"], fill)
         close(N(dcnt), want_dcnt, "DepthFlowProjection count on views, fill %d" % fill)
         close(N(dpo), want_dout, "DepthFlowProjection fwd on views, fill %d" % fill)
+        per_cell(ref[True].ratio_count(N(dcnt)), "DepthFlowProjection count on views, fill %d" % fill)
+        per_cell(ref[True].ratio_out(N(dpo), fill), "DepthFlowProjection fwd on views, fill %d" % fill)
         assert untouched(cnt_b, 1) and untouched(po_b, 2) and untouched(dcnt_b, 1) and untouched(dpo_b, 2)
         if fill == 0:
             gin, gin_b = window(2, fill=7.0)
             assert my_lib.FlowProjectionLayer_gpu_backward(f, cnt, gf, gin) == 0
             close(N(gin), oracle.flow_projection_backward(d["flow"], want_cnt, d["gflow"]), "FlowProjection bwd on views")
+            per_cell(PB.Backward(d["flow"], None, want_cnt, None, d["gflow"]).ratio1(N(gin)), "FlowProjection bwd on views")
             gin2, gin2_b = window(2, fill=7.0)
             gd, gd_b = window(1, fill=7.0)
             # (the SAME forward planes on both sides, as in the contiguous sweep: the library's own differ from the oracle's in the last
@@ -2038,4 +2068,7 @@ def test_random_strided_views_every_operator(oracle, case):
             wg1, wg2 = oracle.depth_flow_projection_backward(d["flow"], d["depth"], want_dcnt, want_dout, d["gflow"])
             close(N(gin2), wg1, "DepthFlowProjection bwd gradinput1 on views")
             close(N(gd), wg2, "DepthFlowProjection bwd gradinput2 on views", cancel=P.CANCEL)
+            bw = PB.Backward(d["flow"], d["depth"], want_dcnt, want_dout, d["gflow"])
+            per_cell(bw.ratio1(N(gin2)), "DepthFlowProjection bwd gradinput1 on views")
+            per_cell(bw.ratio2(N(gd)), "DepthFlowProjection bwd gradinput2 on views")
             assert untouched(gin_b, 2) and untouched(gin2_b, 2) and untouched(gd_b, 1)
