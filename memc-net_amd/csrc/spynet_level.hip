@@ -26,31 +26,8 @@ namespace memc {
 
 thread_local const char *t_spynet_path = "";
 
-// One site: the doubled upsampled flow (ux, uy) and the three channels of `second` sampled at (x, y) + it.  The site
-// arithmetic (level_up_index, level_position, LevelRow, level_flow, level_corners) is memc_spynet_level.hpp's, shared with
-// the backward unit.
-__device__ __forceinline__ void level_site(int x, int y, int W, int H, int w, float sx, float kx, float ky, bool align_up,
-                                           bool align_sample, const LevelRow &r, const float *__restrict__ cb, int64_t scc,
-                                           const float *__restrict__ sb, int64_t ssc, int ssh, float &ux, float &uy,
-                                           float (&warped)[3])
-{
-    level_flow(x, w, sx, align_up, r, cb, scc, ux, uy);
-    const float px = level_position(x, ux, W, kx, align_sample), py = level_position(y, uy, H, ky, align_sample);
-    const LevelCorners k = level_corners(px, py, W, H, ssh);
-    const float wnw = k.bx * k.by, wne = k.ax * k.by, wsw = k.bx * k.ay, wse = k.ax * k.ay;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float *p = sb + c * ssc;
-        const float nw = p[k.r0 + k.cx0], ne = p[k.r0 + k.cx1], sw = p[k.r1 + k.cx0], se = p[k.r1 + k.cx1];
-        float v = 0.0f;
-        v += k.inx0 && k.iny0 ? nw * wnw : 0.0f;
-        v += k.inx1 && k.iny0 ? ne * wne : 0.0f;
-        v += k.inx0 && k.iny1 ? sw * wsw : 0.0f;
-        v += k.inx1 && k.iny1 ? se * wse : 0.0f;
-        warped[c] = v;
-    }
-}
-
+// The site body (level_site) and the arithmetic under it (level_up_index, level_position, LevelRow, level_flow,
+// level_corners) are memc_spynet_level.hpp's, shared with the backward unit and the fp16 / bf16 forward unit.
 // per_row: lanes per output row (QUAD: W / 4, else W).  Strides in elements: f first, s second, c coarse, o out.
 template <bool QUAD>
 __global__ __launch_bounds__(256) void spynet_level(

@@ -1,7 +1,7 @@
-"""What the ctypes bindings of the eighteen satellite libraries share.  All of them: one loader (Library).  The seven warp
+"""What the ctypes bindings of the nineteen satellite libraries share.  All of them: one loader (Library).  The seven warp
 libraries (my_lib_lp, my_lib_lp_grad, my_lib_blend_grad, my_lib_mx, my_lib_mx_grad, my_lib_mx_blend_grad,
 my_lib_lp_blend_grad), the half projection backwards (my_lib_lp_proj_grad, my_lib_lp_dproj_grad), the half bilinear warp (my_lib_lp_bl) and the stacked
-warps and the SPyNet level and its backward (my_lib_stack, my_lib_lp_stack, my_lib_spynet and my_lib_spynet_grad, whose entry points take their ints behind the descriptors and make their own calls): the tensor descriptor, the dtype codes and the call through descriptors (Satellite).  The four that
+warps and the SPyNet level, its backward and its half forward (my_lib_stack, my_lib_lp_stack, my_lib_spynet, my_lib_spynet_grad and my_lib_spynet_lp, whose entry points take their ints behind the descriptors and make their own calls): the tensor descriptor, the dtype codes and the call through descriptors (Satellite).  The four that
 take planes, not NCHW descriptors (my_lib_video, my_lib_ssim, my_lib_video_lp, my_lib_still): the tensor checks and the call
 on plain pointers (check, bytes4, planes, call); the sentences that differ between them are handed in.  Importing this loads
 nothing."""

@@ -17,8 +17,10 @@ with first, second [B, 3, H, W] and coarse [B, 2, h, w], H in {2h, 2h + 1}, W in
 exactly the combination (False, True); the unmodified reference under a current PyTorch computes (False, False), the
 PyTorch 0.2 its checkpoints were trained with (True, True).
 
-The forward kernel serves float32.  The torch expression (`_composed`, the exact composed route) runs instead
-  * on CPU tensors, on other dtypes than float32 and under autocast,
+The forward kernel serves float32; with the class attribute `native_half` set, a second one (libmemc_hip_spynet_lp.so,
+include/memc_spynet_lp.h) serves calls whose three tensors are all float16 or all bfloat16 -- see below.  The torch
+expression (`_composed`, the exact composed route) runs instead
+  * on CPU tensors, on other dtypes than float32 (half dtypes included while `native_half` is False) and under autocast,
   * where the library declines the call (planes beyond 32-bit offsets, a w-stride other than 1),
   * with the class attribute `fused` set to False,
   * whenever gradients are enabled and an input requires one -- such a call keeps torch's autograd through the composed
@@ -35,6 +37,15 @@ declines, the Function composes: the forward returns `_composed`'s values, the b
 `enable_grad` and takes torch's gradient.  `native_backward` ships False (profiles/r27_spynet_level_backward.txt is what a
 change of the default will rest on): a call where `second` requires a gradient, and every call while it is False, keep the
 torch expression.
+The half kernel: with `native_half = True` a call whose three tensors are CUDA, 4-D and of ONE half dtype T, outside
+autocast and with no gradient wanted, allocates `out` in T and makes one launch of libmemc_hip_spynet_lp.so: the float32
+kernel's arithmetic on the exactly widened inputs, every stored element rounded to T once -- bit for bit the float32 kernel
+on the widened inputs followed by `.to(T)`.  Its values are NOT `_composed`'s on half tensors: the torch expression holds
+the linspace grid, the normalised flow and their sum in T, so its sampling positions are rounded to T's grid (for bfloat16
+about 0.9 px apart at a width of 448) before the warp; the kernel forms the position in float32 from the integer site index
+and the unrounded upsampled flow.  That is why `native_half` ships False: it changes what a cast model computes, and
+turning it on is a later decision that rests on profiles/r28_half_spynet_level.txt.  Half calls that want a gradient, mixed
+dtypes and autocast keep the torch expression whatever it says; `native_backward` stays float32-only.
 Values: the upsampled flow and the copy of `first` equal the composed route's to within fp32 rounding (bit for bit where the
 arithmetic is exact); the warp computes the sample position directly instead of through grid_sample's normalise /
 un-normalise round trip, the same function to within fp32 rounding (tests/test_spynet_level_spec.py).
@@ -44,6 +55,7 @@ import torch.nn.functional as F
 
 import my_package._ext.my_lib_spynet as my_lib_spynet
 import my_package._ext.my_lib_spynet_grad as my_lib_spynet_grad
+import my_package._ext.my_lib_spynet_lp as my_lib_spynet_lp
 from ._common import declined
 
 
@@ -104,6 +116,7 @@ class SpyNetLevelLayer(object):
 
     fused = True                                   # False: the torch expression for every call
     native_backward = False                        # True: the gradient of `coarse` by libmemc_hip_spynet_grad.so
+    native_half = False                            # True: all-float16 / all-bfloat16 calls by libmemc_hip_spynet_lp.so
 
     def __init__(self, align_upsample=False, align_sample=False):
         self.align_upsample, self.align_sample = bool(align_upsample), bool(align_sample)
@@ -112,6 +125,16 @@ class SpyNetLevelLayer(object):
         if not self.fused or torch.is_autocast_enabled():
             return False
         if not all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 for t in tensors):
+            return False
+        return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
+
+    def _half_kernel_serves(self, tensors):
+        if not (self.fused and self.native_half) or torch.is_autocast_enabled():
+            return False
+        dtype = tensors[0].dtype
+        if dtype not in (torch.float16, torch.bfloat16):
+            return False
+        if not all(t.is_cuda and t.dtype == dtype and t.dim() == 4 for t in tensors):
             return False
         return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
 
@@ -128,6 +151,12 @@ class SpyNetLevelLayer(object):
             err = my_lib_spynet.SpyNetLevelLayer_gpu_forward(first, second, coarse, out, self.align_upsample,
                                                              self.align_sample)
             if not declined(err, "SpyNetLevelLayer_gpu_forward"):
+                return out
+        elif self._half_kernel_serves((first, second, coarse)):
+            out = first.new_empty((first.size(0), 8, first.size(2), first.size(3)))
+            err = my_lib_spynet_lp.SpyNetLevelLayer_gpu_forward_lp(first, second, coarse, out, self.align_upsample,
+                                                                   self.align_sample)
+            if not declined(err, "SpyNetLevelLayer_gpu_forward_lp"):
                 return out
         elif self._backward_kernel_serves(first, second, coarse):
             return _SpyNetLevelFunction.apply(first, second, coarse, self.align_upsample, self.align_sample)

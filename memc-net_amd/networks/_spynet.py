@@ -20,7 +20,11 @@ Differences, deliberate:
   * `fused_level_backward`: in a training step, where a level's coarse flow wants a gradient and its frames are data, the
     level input through the same layer's autograd Function -- the forward kernel, and one backward kernel for the gradient
     of the coarse flow (libmemc_hip_spynet_grad.so) instead of torch's autograd through the torch expression.  Off by
-    default.
+    default;
+  * `fused_level_half`: in a model cast to bfloat16 / float16, a level's input by the half-precision kernel
+    (libmemc_hip_spynet_lp.so) where all three tensors are of one half dtype, autocast is off and no gradient is wanted,
+    instead of the torch expression on half tensors.  Off by default: it changes the values a cast model computes (the
+    kernel forms the sampling position in float32; the torch expression rounds its grid and flow to the half dtype first).
 """
 import torch
 import torch.nn as nn
@@ -95,17 +99,23 @@ class SPyNet(nn.Module):
         # of torch's autograd through the torch expression.  Ships off whatever profiles/r27_spynet_level_backward.txt says:
         # the default training route is the one the existing tests pin
         self.fused_level_backward = False
+        # a cast model's level input by the half kernel (my_package.functions.SpyNetLevelLayer.native_half) instead of the
+        # torch expression on half tensors.  Ships off whatever profiles/r28_half_spynet_level.txt says: the kernel changes
+        # the values a cast model computes (its sampling position is float32, not rounded to the half dtype)
+        self.fused_level_half = False
         self.moduleBasic = nn.ModuleList([_Basic() for _ in range(LEVELS)])
 
     def level_input(self, first, second, coarse):
         """The [B, 8, H, W] input of one level's convolutions, by the route `fused_level` selects: the only place it is made.
         With my_package's extension it is the layer's business either way (its kernel, or its own torch expression for CPU
         tensors, other dtypes, autocast, declined calls, inputs that want a gradient and `fused_level = False`; with
-        `fused_level_backward` its backward kernel where only the coarse flow wants a gradient)."""
+        `fused_level_backward` its backward kernel where only the coarse flow wants a gradient, with `fused_level_half`
+        its half kernel where all three tensors are of one half dtype)."""
         if SpyNetLevelModule is not None:
             level = SpyNetLevelModule(self.align_upsample, self.align_sample)
             level.f.fused = bool(self.fused_level)
             level.f.native_backward = bool(self.fused_level_backward)
+            level.f.native_half = bool(self.fused_level_half)
             return level(first, second, coarse)
         return level_input_composed(first, second, coarse, self.align_upsample, self.align_sample)
 

@@ -5,7 +5,7 @@ scene directory, interpolate the frame between frame10.png and frame11.png and s
     python tools/demo_middlebury.py --data other-data --gt other-gt-interp --output results
                                     [--model {MEMC_Net_star,MEMC_Net,MEMC_Net_s} --weights best.pth --align-corners] [--save-which 1]
                                     [--precision {fp32,bf16,fp16,autocast-bf16,autocast-fp16}]
-                                    [--gpu-io] [--scenes-per-step N] [--ssim]
+                                    [--gpu-io] [--scenes-per-step N] [--ssim] [--fused-half-level]
                                     [--first im1.png --second im3.png --middle im2.png]
 
 Each pair is replicate-padded to multiples of 128 like demo_MiddleBury.py:98-117 and cropped back; results/<scene>/ receives
@@ -17,7 +17,9 @@ fp16) or a float32 model under torch.autocast.  --gpu-io does the pixel work aro
 quantisation, error sums, difference picture) on the device: the same bytes and numbers; --scenes-per-step N sends up to N
 consecutive scenes of one size through the network at once; --ssim adds the RGB SSIM (the mean over the three channels, as
 demo_Vimeo_VE.py:168 reports it) as a third column.  --first / --second / --middle name the files of a scene, so that a
-Vimeo-90K tree (im1.png, im3.png, im2.png) runs as it is.  Needs a GPU: the operators have no CPU path.
+Vimeo-90K tree (im1.png, im3.png, im2.png) runs as it is.  --fused-half-level (MEMC_Net_s under --precision bf16 / fp16): the
+flow estimator's pyramid-level inputs by the half-precision kernel (libmemc_hip_spynet_lp.so) instead of the torch expression
+on half tensors; off by default, since it changes the values a cast model computes.  Needs a GPU: the operators have no CPU path.
 """
 import argparse
 import os
@@ -49,6 +51,10 @@ def main(argv=None):
     ap.add_argument("--scenes-per-step", type=int, default=1, metavar="N",
                     help="consecutive scenes of one size that go through the network as one batch (default 1)")
     ap.add_argument("--ssim", action="store_true", help="also report the RGB SSIM (mean over the three channels)")
+    ap.add_argument("--fused-half-level", action="store_true",
+                    help="MEMC_Net_s cast to bf16 / fp16: SPyNet's level inputs by the half-precision kernel (sets "
+                         "flownets.fused_level_half; off by default: the kernel samples at float32 positions, the torch "
+                         "expression at positions rounded to the half dtype)")
     ap.add_argument("--first", default="frame10.png", help="file name of a scene's first frame")
     ap.add_argument("--second", default="frame11.png", help="file name of a scene's second frame")
     ap.add_argument("--middle", default="frame10i11.png", help="file name of the frame in between (output and ground truth)")
@@ -79,6 +85,10 @@ def main(argv=None):
     autocast = half.get(a.precision[len("autocast-"):]) if a.precision.startswith("autocast-") else None
     if dtype is not None:
         net = net.to(dtype)
+    if a.fused_half_level:
+        if a.model != "MEMC_Net_s":
+            raise SystemExit("--fused-half-level: only MEMC_Net_s has a SPyNet flow estimator")
+        net.flownets.fused_level_half = True
     os.makedirs(a.output, exist_ok=True)
     kw = dict(dtype=dtype, autocast=autocast) if a.precision != "fp32" else {}
     for name, value, default in (("first", a.first, "frame10.png"), ("second", a.second, "frame11.png"),
